@@ -15,13 +15,17 @@ reduction and the dt control), counted exactly like the reference's figure of me
           for 8 ranks), ghost strips travel as RCCL point-to-point messages overlapped with the update of the boxes that need
           nothing remote.  `weak_256_per_gpu` is the same measurement with 256^3 cells per rank.
 
-Output: ONE JSON line on rank 0 (see the contract in the task statement), including
+Output: ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, steps, warmup, config).  A plain run does
+only that: set up, `--warmup` untimed steps, exactly `--steps` timed steps, the line.  `--full` adds what takes runs or passes of its own:
   roofline     — algorithmic bytes of the dominant fused sweep kernel / its HIP-event duration vs 8 TB/s HBM, every sweep listed
+  repeats, the secondary figures above, the shader clock during the timed steps, (N > 1) the inline self-test before them
   cpu_baseline — the CPU oracle (a port of the reference algorithm, NOT the reference binary) on the host cores (N = 1 only)
+`--dump-outputs DIR` writes the state the last timed step left (a fixed sample, see dump_outputs) as DIR/*.npy.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import glob
 import json
@@ -33,6 +37,7 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")  # the reference's problem files compiled against the C++ host (__graft_entry__.build_refproblems)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 # algorithmic bytes per cell-sweep of the fused PPM+HLLC sweep kernels and of the flattening pre-pass
@@ -90,6 +95,12 @@ def parse():
     ap.add_argument("--long-steps", type=int, default=100, help="steps (and warm-up steps) of the long_run secondary figure")
     ap.add_argument("--cpu-ncell", type=int, default=128)
     ap.add_argument("--cpu-steps", type=int, default=400)  # at most; the sample ends after ~12 s of wall time (cpu_baseline)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and per-kernel tables, shader clock, repeats, the secondary figures, the CPU "
+                         "baselines and (N > 1) the inline self-test.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; a fixed sample of the state, see "
+                         "dump_outputs)")
     return ap.parse_args()
 
 
@@ -229,9 +240,10 @@ def read_profile(ctx):
     return kernels
 
 
-def run_shell(ctx, torch, ncell, mgs, steps, warmup, pow_mode, carry=False):
+def run_shell(ctx, torch, ncell, mgs, steps, warmup, pow_mode, carry=False, dump=None):
     """BASELINE config 4: RadhydroShell (tests/radhydro_shell_256.in; the reference problem runs 50 steps, test_radhydro_shell.cpp:431), one update =
-    hydro RK2 + all radiation substeps.  Returns the JSON object of the line (headline with --workload shell, `shell256` block otherwise)."""
+    hydro RK2 + all radiation substeps.  Returns the JSON object of the line (headline with --workload shell, `shell256` block otherwise).
+    dump: called with the simulation right after the timed steps (--dump-outputs)."""
     import numpy as np
     from quokka_amd.radhydro import shell_problem
     tab = np.loadtxt(os.path.join(ROOT, "tests", "golden", "dust_shell_initial_conditions.txt"), skiprows=1)
@@ -251,6 +263,8 @@ def run_shell(ctx, torch, ncell, mgs, steps, warmup, pow_mode, carry=False):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     L.qk_profile_enable(ctx.h, 0)
+    if dump is not None:
+        dump(sim)
     kernels = read_profile(ctx)
     mass1 = sum(float(sim.state_new_cc_.valid(b)[0].sum().item()) for b in range(sim.lev.nboxes))
     total_cells = ncell ** 3
@@ -365,15 +379,15 @@ def cxx_host_block(args, ncell):
 
 
 def full_run_block(args):
-    """The metric as the reference counts it (src/simulation.hpp:972-981, :1285): bin/ref_HydroBlast3D — the reference's own problem file,
+    """The metric as the reference counts it (src/simulation.hpp:972-981, :1285): oracle/_ref/ref_HydroBlast3D — the reference's own problem file,
     compiled unchanged against the C++17 host — with the deck of BASELINE config 2 (blast_unigrid_256.in: max_timesteps = 1000), cell-updates
     divided by the wall time of the WHOLE evolve as the executable prints it, both forms of the RK2 average, plus how often the first-order flux
     correction and the retry loop ran (a line this host adds after the figure of merit)."""
     import subprocess
     host = os.path.join(ROOT, "quokka_amd", "host")
-    exe = os.path.join(host, "bin", "ref_HydroBlast3D")
+    exe = os.path.join(REF_BIN, "ref_HydroBlast3D")
     if not os.path.exists(exe):
-        return {"error": "quokka_amd/host/bin/ref_HydroBlast3D is not built (needs the reference tree at build time)"}
+        return {"error": "oracle/_ref/ref_HydroBlast3D is not built (needs the reference tree at build time)"}
     out = {"unit": "Mcell-updates/s", "deck": "quokka_amd/host/decks/blast_unigrid_256.in (the keys of the reference's tests/blast_unigrid_256.in), unchanged: 1000 steps",
            "driver": "the reference's test_hydro3d_blast.cpp, unchanged, through QuokkaSimulation<problem_t> (C++17 host mirror); the executable's own "
                      "figure of merit: all cell-updates / wall time of evolve()"}
@@ -567,9 +581,9 @@ def cxx_shell_block(args, steps=22):
     import re
     import subprocess
     host = os.path.join(ROOT, "quokka_amd", "host")
-    exe = os.path.join(host, "bin", "ref_RadhydroShell")
+    exe = os.path.join(REF_BIN, "ref_RadhydroShell")
     if not os.path.exists(exe):
-        return {"error": "quokka_amd/host/bin/ref_RadhydroShell is not built (needs the reference tree at build time)"}
+        return {"error": "oracle/_ref/ref_RadhydroShell is not built (needs the reference tree at build time)"}
     gold = os.path.join(ROOT, "tests", "golden", "dust_shell_initial_conditions.txt")
     import tempfile
     vals = {}
@@ -605,9 +619,9 @@ def cxx_amr_block(args, steps=55, skip=5):
     Python block times (coarse steps skip + 1 .. steps), from the difference of two runs."""
     import subprocess
     host = os.path.join(ROOT, "quokka_amd", "host")
-    exe = os.path.join(host, "bin", "ref_HydroBlast3D")
+    exe = os.path.join(REF_BIN, "ref_HydroBlast3D")
     if not os.path.exists(exe):
-        return {"error": "quokka_amd/host/bin/ref_HydroBlast3D is not built (needs the reference tree at build time)"}
+        return {"error": "oracle/_ref/ref_HydroBlast3D is not built (needs the reference tree at build time)"}
     carry = 1 if args.rk2_mode == "carry" else 0
 
     def run(n):
@@ -703,8 +717,9 @@ def selftest(ctx, torch, dist, rank, world, carry, inline=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------- Sedov runs
-def run_sedov(ctx, torch, dist, rank, world, ncell, mgs, steps, warmup, profile=True, carry=False):
-    """build the problem, `warmup` untimed steps, then EXACTLY `steps` timed steps between barrier + synchronize pairs; max over ranks"""
+def run_sedov(ctx, torch, dist, rank, world, ncell, mgs, steps, warmup, profile=True, carry=False, clock=True):
+    """build the problem, `warmup` untimed steps, then EXACTLY `steps` timed steps between barrier + synchronize pairs; max over ranks.
+    clock: sample the shader clock during the timed steps (ClockSampler)"""
     from quokka_amd.simulation import sedov_problem
     n_cell = weak_scaled_cells(ncell, world)
     sim = sedov_problem(ctx, ncell, max_grid_size=mgs, rank=rank, nranks=world, n_cell=n_cell)
@@ -729,14 +744,14 @@ def run_sedov(ctx, torch, dist, rank, world, ncell, mgs, steps, warmup, profile=
     if world > 1:
         sim.ghost.exposed_events = []  # (two event records per fill: how long the compute stream stalls for the peers' strips)
     barrier()
-    clk = ClockSampler(torch, ctx.device.index if hasattr(ctx.device, "index") and ctx.device.index is not None else 0)
+    clk = ClockSampler(torch, ctx.device.index if hasattr(ctx.device, "index") and ctx.device.index is not None else 0) if clock else None
     t0 = time.perf_counter()
-    with clk:
+    with clk or contextlib.nullcontext():
         for _ in range(steps):
             assert sim.step(), "hydro advance failed"
         barrier()
     elapsed = time.perf_counter() - t0
-    sim.clock_during_timed_steps = clk.summary()
+    sim.clock_during_timed_steps = clk.summary() if clk else None
     if profile:
         L.qk_profile_enable(ctx.h, 0)
         L.qk_profile_only(ctx.h, None)
@@ -764,6 +779,50 @@ def run_sedov(ctx, torch, dist, rank, world, ncell, mgs, steps, warmup, profile=
             L.qk_profile_get(ctx.h, k, C.byref(name), C.byref(cnt), C.byref(ms))
             kernels[name.value.decode()] = (cnt.value, ms.value)
     return sim, n_cell, elapsed, kernels
+
+
+def dump_outputs(path, sim, n_cell, ctx, torch, dist, world, rank, sample_cells=1 << 19, corner=64):
+    """--dump-outputs: the state the last timed step left in sim.state_new_cc_ (the conserved components of every cell), as float64 .npy files
+    in `path`.  The whole state is too large (256^3: 805 MB), so a fixed part of it, the same for every run with the same arguments:
+      state_sample  (ncomp, m)      m cells drawn with a fixed seed from the whole domain (flat index x fastest), sorted
+      state_corner  (ncomp, c, c, c) the c^3 cells at the origin, [comp, z, y, x] (where the blast starts)
+      state_sums    (ncomp,)         every component summed over the domain
+      time_dt       (2,)             simulation time and the last time step
+    With N ranks every rank fills in the cells of its own boxes and the parts are summed (each cell lives on one rank); rank 0 writes."""
+    import numpy as np
+    ncomp = int(sim.state_new_cc_.valid(0).shape[0])
+    nx, ny, nz = (int(v) for v in n_cell)
+    while corner > 8 and ncomp * corner ** 3 * 8 > (16 << 20):
+        corner //= 2
+    corner = min(corner, nx, ny, nz)
+    m = min(sample_cells, nx * ny * nz, (40 << 20) // (8 * ncomp))
+    flat = np.sort(np.random.default_rng(20261016).integers(0, nx * ny * nz, size=m))
+    ii, jj, kk = flat % nx, (flat // nx) % ny, flat // (nx * ny)
+    dev = ctx.device
+    sample = torch.zeros((ncomp, m), dtype=torch.float64, device=dev)
+    block = torch.zeros((ncomp, corner, corner, corner), dtype=torch.float64, device=dev)
+    sums = torch.zeros((ncomp,), dtype=torch.float64, device=dev)
+    for b, (lo, hi) in enumerate(sim.my_boxes):
+        v = sim.state_new_cc_.valid(b)
+        sel = np.nonzero((ii >= lo[0]) & (ii <= hi[0]) & (jj >= lo[1]) & (jj <= hi[1]) & (kk >= lo[2]) & (kk <= hi[2]))[0]
+        if sel.size:
+            idx = [torch.from_numpy(a[sel] - o).to(dev) for a, o in ((kk, lo[2]), (jj, lo[1]), (ii, lo[0]))]
+            sample[:, torch.from_numpy(sel).to(dev)] = v[:, idx[0], idx[1], idx[2]].to(torch.float64)
+        if all(lo[d] < corner for d in range(3)):
+            ext = [min(hi[d], corner - 1) - lo[d] + 1 for d in range(3)]
+            block[:, lo[2]:lo[2] + ext[2], lo[1]:lo[1] + ext[1], lo[0]:lo[0] + ext[0]] = v[:, :ext[2], :ext[1], :ext[0]]
+        sums += v.to(torch.float64).sum(dim=(1, 2, 3))
+    if world > 1:
+        from quokka_amd import comm
+        for t in (sample, block, sums):
+            comm.all_reduce(t, dist.ReduceOp.SUM)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {"state_sample": sample, "state_corner": block, "state_sums": sums,
+              "time_dt": torch.tensor([float(sim.tNew_), float(sim.dt_)], dtype=torch.float64)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy().astype(np.float64))
 
 
 def roofline_of(kernels, cells_local, total_cells, steps, elapsed, world, ncell, mgs, kernels_all=None):
@@ -861,8 +920,10 @@ def main():
         v = selftest(ctx, torch, dist, rank, world, carry=(args.rk2_mode == "carry"))
         sys.exit(0 if (rank != 0 or v["selftest"] == "PASS") else 1)
     ncell = args.ncell if args.ncell is not None else (256 if world == 1 else 512)
+    if args.dump_outputs and args.workload not in ("sedov", "shell"):
+        raise SystemExit(f"--dump-outputs: the sedov and shell workloads only (not {args.workload})")
     selftest_verdict = None
-    if world > 1 and args.workload == "sedov":
+    if world > 1 and args.workload == "sedov" and args.full:
         # the exchange path proves itself before it is timed: N ranks against one rank, bit for bit (a hang becomes a FAIL line, see selftest)
         selftest_verdict = selftest(ctx, torch, dist, rank, world, carry=(args.rk2_mode == "carry"), inline=True)
     if args.workload == "shell_amr":
@@ -902,17 +963,20 @@ def main():
 
     if args.workload == "shell":
         assert world == 1, "the shell line is single-GPU"
-        out = run_shell(ctx, torch, args.ncell if args.ncell is not None else 256, args.max_grid_size, args.steps, args.warmup, args.pow_mode,
-                        carry=(args.rk2_mode == "carry"))
-        if not args.no_cpu_baseline:
+        n_shell = args.ncell if args.ncell is not None else 256
+        dump = (lambda s: dump_outputs(args.dump_outputs, s, [n_shell] * 3, ctx, torch, dist, 1, 0)) if args.dump_outputs else None
+        out = run_shell(ctx, torch, n_shell, args.max_grid_size, args.steps, args.warmup, args.pow_mode, carry=(args.rk2_mode == "carry"), dump=dump)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_shell()
         print(json.dumps(out), flush=True)
         return
 
     # ------------------------------------------------------------------------------------------------------------ Sedov (headline)
     mgs = args.max_grid_size
-    sim, n_cell, elapsed, kernels = run_sedov(ctx, torch, dist, rank, world, ncell, mgs, args.steps, args.warmup, carry=(args.rk2_mode == "carry"))
-    cells_local = sim.lev.num_cells()
+    sim, n_cell, elapsed, kernels = run_sedov(ctx, torch, dist, rank, world, ncell, mgs, args.steps, args.warmup, carry=(args.rk2_mode == "carry"),
+                                              profile=args.full, clock=args.full)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, n_cell, ctx, torch, dist, world, rank)
     total_cells = n_cell[0] * n_cell[1] * n_cell[2]
     groups = sim.overlap_groups() if world > 1 else None
     out = {
@@ -935,14 +999,30 @@ def main():
                    "clock": getattr(sim, "clock_during_timed_steps", None),
                    "note": "N = 1 runs BASELINE config 2 (256^3); N > 1 runs 512^3 cells per GPU (N = 8: config 3, 1024^3); "
                            "weak_256_per_gpu is the same geometry as N = 1 on every rank"},
-        "roofline": None,  # (filled below, after the pass that times every kernel)
         # context only (other hardware, reference implementation): paper/performance_a100.csv:2 = 254.05 Mzones/s on 1x A100
         "reference_published_a100_1gpu": 254.05,
     }
-    if world > 1:
+    if world > 1 and args.full:
         out["selftest"] = selftest_verdict  # (rank 0's; None on the other ranks, which do not print)
     if share:
         out["dry_run"] = f"{world} ranks share cuda:0 and talk over gloo with host-staged buffers: the SHAPE of the N > 1 line on a small problem, never a measurement"
+    if args.full:
+        repeats_and_roofline(args, out, ctx, torch, dist, world, sim, ncell, mgs, n_cell, elapsed, kernels)
+    del sim
+    torch.cuda.empty_cache()
+    if args.full:
+        secondary_figures(args, out, ctx, torch, dist, rank, world, ncell, mgs, share)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def repeats_and_roofline(args, out, ctx, torch, dist, world, sim, ncell, mgs, n_cell, elapsed, kernels):
+    """--full: the headline's run continued — the roofline object (with a pass that times every kernel) and the repeats"""
+    cells_local = sim.lev.num_cells()
+    total_cells = n_cell[0] * n_cell[1] * n_cell[2]
     # the same measurement twice more on the same run (the box's HBM rate drifts by several percent within minutes: profiles/round4/README.md)
     reps = []
     kernels_all = None
@@ -973,8 +1053,10 @@ def main():
     out["repeats"] = {"values": [total_cells * args.steps / r / 1e6 for r in reps], "unit": "Mcell-updates/s", "steps_each": args.steps,
                       "note": "the timed region repeated twice on the continuing run, after `value` was taken: the first with HIP events around every "
                               "kernel (the roofline table), the second with none"}
-    del sim
-    torch.cuda.empty_cache()
+
+
+def secondary_figures(args, out, ctx, torch, dist, rank, world, ncell, mgs, share):
+    """--full: the secondary figures of the Sedov line, each on a run of its own after the headline, and the CPU baseline"""
     if not args.no_secondary:
         if world == 1 and ncell == 256:
             # (a) developed-run figure: the default timed region sits at sim-time ~6e-5; >= 100 + 100 steps moves the shock further out
@@ -1034,13 +1116,8 @@ def main():
             blk = run_amr(ctx, torch, dist, rank, world, 64 if share else 256, 4 if share else 30, 1 if share else 5)
             out["amr_maxlev2"] = compact(blk, keep=("value", "unit", "steps", "warmup", "ms_per_step", "scaling", "config"))
             torch.cuda.empty_cache()
-    if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_ncell, args.cpu_steps)
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank == 0 and not args.no_cpu_baseline and world == 1:
+        out["cpu_baseline"] = cpu_baseline(args.cpu_ncell, args.cpu_steps)
 
 
 def cpu_baseline_shell(ncell: int = 32, steps: int = 2):

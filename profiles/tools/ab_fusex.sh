@@ -5,7 +5,7 @@ out=gpurun_out/ab_fusex.txt
 for n in 256 512; do
   for rep in 1 2; do
     for f in 0 1; do
-      QK_FUSEX=$f python bench.py --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+      QK_FUSEX=$f python bench.py --full --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 k = (d.get('roofline') or {}).get('all_kernels_ms_per_launch') or {}

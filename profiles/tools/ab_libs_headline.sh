@@ -8,7 +8,7 @@ out=gpurun_out/ab_libs_headline.txt
 for n in ${@:-256}; do
   for rep in 1 2 3; do
     for lib in $A $B; do
-      QK_LIB_PATH=$PWD/$lib python bench.py --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+      QK_LIB_PATH=$PWD/$lib python bench.py --full --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={a:round(b,4) for a,b in d['roofline'].get('all_kernels_ms_per_launch',{}).items()}

@@ -8,7 +8,7 @@ out=gpurun_out/ab_pre_prefetch.txt
 for n in 256 512; do
   for rep in 1 2 3; do
     for v in "" _pf1 _pf2; do
-      QK_LIB_PATH=$PWD/quokka_amd/lib/libquokka_amd$v.so python bench.py --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+      QK_LIB_PATH=$PWD/quokka_amd/lib/libquokka_amd$v.so python bench.py --full --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={a:round(b,4) for a,b in d['roofline'].get('all_kernels_ms_per_launch',{}).items()}

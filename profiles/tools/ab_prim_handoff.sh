@@ -8,7 +8,7 @@ out=gpurun_out/ab_prim_handoff.txt
 for n in 256 512; do
   for rep in 1 2 3; do
     for ph in 0 1; do
-      QK_PRIM_HANDOFF=$ph python bench.py --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+      QK_PRIM_HANDOFF=$ph python bench.py --full --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 k={a:round(b,4) for a,b in d['roofline'].get('all_kernels_ms_per_launch',{}).items()}

@@ -4,7 +4,7 @@ n=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
     lib=quokka_amd/lib/variants/libqk_$v.so; [ "$v" = base ] && lib=quokka_amd/lib/libquokka_amd.so
-    QK_LIB_PATH=$PWD/$lib python bench.py --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+    QK_LIB_PATH=$PWD/$lib python bench.py --full --ncell $n --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 k = (d.get('roofline') or {}).get('all_kernels_ms_per_launch') or {}

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; B=$R/quokka_amd/host
 for o in 0 1; do
   O=$R/gpurun_out/cxx_amr_conc_$o; rm -rf $O; mkdir -p $O
-  (cd $B && rocprofv3 --kernel-trace --output-format csv -d $O/kt -- $B/bin/ref_HydroBlast3D $B/decks/blast_amr_maxlev2.in max_timesteps=55 hydro.rk2_carry_rhs=1 plotfile_interval=-1 checkpoint_interval=-1 qk.overlap_children=$o > $O/run.log 2>&1)
+  (cd $B && rocprofv3 --kernel-trace --output-format csv -d $O/kt -- $R/oracle/_ref/ref_HydroBlast3D $B/decks/blast_amr_maxlev2.in max_timesteps=55 hydro.rk2_carry_rhs=1 plotfile_interval=-1 checkpoint_interval=-1 qk.overlap_children=$o > $O/run.log 2>&1)
   grep -E "figure-of-merit|speculative" $O/run.log | tr '\n' ' '; echo
   python - "$O" <<'PY'
 import csv, glob, sys, collections

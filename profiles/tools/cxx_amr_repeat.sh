@@ -5,7 +5,7 @@ reps=${1:-8}; shift
 R=$GRAFT_REPO_ROOT; B=$R/quokka_amd/host; W=/tmp/cxx_amr_repeat; rm -rf $W; mkdir -p $W
 for r in $(seq 1 $reps); do
   mkdir -p $W/$r; cd $W/$r
-  $B/bin/ref_HydroBlast3D $B/decks/blast_amr_maxlev2.in max_timesteps=40 hydro.rk2_carry_rhs=1 plotfile_interval=100000 checkpoint_interval=-1 "$@" > log 2>&1
+  $R/oracle/_ref/ref_HydroBlast3D $B/decks/blast_amr_maxlev2.in max_timesteps=40 hydro.rk2_carry_rhs=1 plotfile_interval=100000 checkpoint_interval=-1 "$@" > log 2>&1
   d=$(ls -d plt* 2>/dev/null | tail -1)
   if [ -z "$d" ]; then echo "run $r: no plotfile"; tail -3 log; continue; fi
   (cd $d && find . -name "Cell_D_*" | sort | xargs cat | md5sum | cut -c1-12) > digest

@@ -4,7 +4,7 @@
 cd quokka_amd/host
 for rep in 1 2; do
   for o in 0 1; do
-    ./bin/ref_HydroBlast3D decks/blast_amr_maxlev2.in max_timesteps=55 hydro.rk2_carry_rhs=1 plotfile_interval=-1 checkpoint_interval=-1 qk.overlap_children=$o 2>&1 | grep -E "figure-of-merit|speculative|Energy conservation" | tr '\n' ' ' | sed "s/^/cxx overlap_children=$o rep $rep: /"; echo
+    ../../oracle/_ref/ref_HydroBlast3D decks/blast_amr_maxlev2.in max_timesteps=55 hydro.rk2_carry_rhs=1 plotfile_interval=-1 checkpoint_interval=-1 qk.overlap_children=$o 2>&1 | grep -E "figure-of-merit|speculative|Energy conservation" | tr '\n' ' ' | sed "s/^/cxx overlap_children=$o rep $rep: /"; echo
   done
 done
 cd ../..

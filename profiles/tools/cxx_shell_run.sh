@@ -4,5 +4,5 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 steps=${1:-22}; shift
 tmp=$(mktemp -d); cp $R/tests/golden/dust_shell_initial_conditions.txt $tmp/initial_conditions.txt; cd $tmp
-$R/quokka_amd/host/bin/ref_RadhydroShell $R/quokka_amd/host/decks/radhydro_shell_256.in max_timesteps=$steps plotfile_interval=-1 checkpoint_interval=-1 hydro.rk2_carry_rhs=1 "$@" 2>&1 | grep -E "figure-of-merit|elapsed time|abort" | head -4
+$R/oracle/_ref/ref_RadhydroShell $R/quokka_amd/host/decks/radhydro_shell_256.in max_timesteps=$steps plotfile_interval=-1 checkpoint_interval=-1 hydro.rk2_carry_rhs=1 "$@" 2>&1 | grep -E "figure-of-merit|elapsed time|abort" | head -4
 rm -rf $tmp

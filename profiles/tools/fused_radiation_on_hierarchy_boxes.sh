@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." && mkdir -p gpurun_out/r6/fr && cd gpurun_out/r6/fr &
 cp $R/tests/golden/dust_shell_initial_conditions.txt initial_conditions.txt
 
 for f in 0 1; do
-  QK_AMR_VERBOSE=1 $R/quokka_amd/host/bin/ref_RadhydroShell $R/quokka_amd/host/decks/radhydro_shell_amr.in amr.n_cell="32 32 32" amr.max_level=1 amr.blocking_factor=8 amr.max_grid_size=32 max_timesteps=4 qk.fused_radiation=$f qk.dump_state=s$f.bin > log$f.txt 2>&1
+  QK_AMR_VERBOSE=1 $R/oracle/_ref/ref_RadhydroShell $R/quokka_amd/host/decks/radhydro_shell_amr.in amr.n_cell="32 32 32" amr.max_level=1 amr.blocking_factor=8 amr.max_grid_size=32 max_timesteps=4 qk.fused_radiation=$f qk.dump_state=s$f.bin > log$f.txt 2>&1
   grep -c "makeLevel" log$f.txt; grep "makeLevel" log$f.txt | tail -1 | cut -c1-400
 done
 python - <<PY

@@ -42,7 +42,7 @@ def run(exe, args, cwd, nranks, steps):
     for r in range(nranks):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(nranks), LOCAL_RANK=str(r), MASTER_PORT=str(28000 + _tag[0]), MASTER_ADDR="127.0.0.1", QK_COMM_BACKEND="shm",
                    QK_COMM_TIMEOUT="120", QK_MAX_COARSE_STEPS=str(steps), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([os.path.join(HOST, "bin", exe)] + args, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        procs.append(subprocess.Popen([os.path.join(ROOT, "oracle", "_ref", exe)] + args, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [p.communicate(timeout=900)[0] for p in procs]
     plots = re.findall(r"Writing plotfile (\S+)", outs[0])
     return [p.returncode for p in procs], outs, (os.path.join(cwd, plots[-1]) if plots else None)

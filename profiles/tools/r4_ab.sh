@@ -8,12 +8,12 @@ mkdir -p "$out"
 for rep in 1 2; do
   for spec in "$@"; do
     label=${spec%%|*}; envs=${spec#*|}
-    env $envs python bench.py --no-secondary --no-cpu-baseline $extra > "$out/ab_${label}_256_$rep.json" 2> "$out/ab_${label}_256_$rep.err"
+    env $envs python bench.py --full --no-secondary --no-cpu-baseline $extra > "$out/ab_${label}_256_$rep.json" 2> "$out/ab_${label}_256_$rep.err"
   done
 done
 for spec in "$@"; do
   label=${spec%%|*}; envs=${spec#*|}
-  env $envs python bench.py --no-secondary --no-cpu-baseline --ncell 512 --steps 8 --warmup 2 $extra > "$out/ab_${label}_512.json" 2> "$out/ab_${label}_512.err"
+  env $envs python bench.py --full --no-secondary --no-cpu-baseline --ncell 512 --steps 8 --warmup 2 $extra > "$out/ab_${label}_512.json" 2> "$out/ab_${label}_512.err"
 done
 python - "$out" <<'PY'
 import glob, json, os, sys

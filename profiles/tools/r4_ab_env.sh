@@ -5,11 +5,11 @@ out=$1; var=$2; vals=$3; shift 3
 mkdir -p "$out"
 for rep in 1 2; do
   for v in $vals; do
-    env $var=$v python bench.py --no-secondary --no-cpu-baseline "$@" > "$out/ab_${var}_${v}_256_$rep.json" 2> "$out/ab_${var}_${v}_256_$rep.err"
+    env $var=$v python bench.py --full --no-secondary --no-cpu-baseline "$@" > "$out/ab_${var}_${v}_256_$rep.json" 2> "$out/ab_${var}_${v}_256_$rep.err"
   done
 done
 for v in $vals; do
-  env $var=$v python bench.py --no-secondary --no-cpu-baseline --ncell 512 --steps 8 --warmup 2 "$@" > "$out/ab_${var}_${v}_512.json" 2> "$out/ab_${var}_${v}_512.err"
+  env $var=$v python bench.py --full --no-secondary --no-cpu-baseline --ncell 512 --steps 8 --warmup 2 "$@" > "$out/ab_${var}_${v}_512.json" 2> "$out/ab_${var}_${v}_512.err"
 done
 python - "$out" "$var" <<'PY'
 import glob, json, os, sys

@@ -6,9 +6,9 @@ OUT=gpurun_out/r6/bisect; mkdir -p $OUT/one $OUT/many; cd $OUT
 R=../../../..
 for K in ${STEPS:-1 2 3 4 5 6}; do
   s=$(printf "%05d" $K)
-  (cd one; rm -rf plt*; QK_MAX_COARSE_STEPS=$K $R/quokka_amd/host/bin/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 checkpoint_interval=-1 amr.max_grid_size=8 \
+  (cd one; rm -rf plt*; QK_MAX_COARSE_STEPS=$K $R/oracle/_ref/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 checkpoint_interval=-1 amr.max_grid_size=8 \
      qk.cluster_within_parent=1 ${EXTRA} > log.txt 2>&1)
-  (cd many; rm -rf plt*; QK_AMR_VERBOSE=1 QK_MAX_COARSE_STEPS=$K TMO=60 TAIL=1 $R/profiles/tools/run_cxx_ranks.sh 4 . $R/quokka_amd/host/bin/ref_RadBeam $R/quokka_amd/host/decks/beam.in \
+  (cd many; rm -rf plt*; QK_AMR_VERBOSE=1 QK_MAX_COARSE_STEPS=$K TMO=60 TAIL=1 $R/profiles/tools/run_cxx_ranks.sh 4 . $R/oracle/_ref/ref_RadBeam $R/quokka_amd/host/decks/beam.in \
      plotfile_interval=-1 checkpoint_interval=-1 amr.max_grid_size=8 qk.level0_distribution=interleaved qk.distribute_levels=0 ${EXTRA} > log.txt 2>&1)
   echo "=== K = $K"; grep -h "radiation source" many/rank*.log | head -3
   python ../../../profiles/tools/compare_plotfiles.py one/plt$s many/plt$s 2>&1 | grep -v "level 0 boxes" | cut -c1-260

@@ -6,9 +6,9 @@ cd "$(dirname "$0")/../.." || exit 1
 OUT=${OUT:-gpurun_out/r6/ctl}; mkdir -p $OUT; cd $OUT
 R=../../..
 for st in 8 10 12 16 20; do
-  QK_MAX_COARSE_STEPS=$st $R/quokka_amd/host/bin/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 checkpoint_interval=-1 amr.max_grid_size=${MGS:-32} \
+  QK_MAX_COARSE_STEPS=$st $R/oracle/_ref/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 checkpoint_interval=-1 amr.max_grid_size=${MGS:-32} \
      qk.cluster_within_parent=1 qk.dump_state=one.bin > one.log 2>&1
-  QK_MAX_COARSE_STEPS=$st TMO=60 TAIL=1 $R/profiles/tools/run_cxx_ranks.sh 4 . $R/quokka_amd/host/bin/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 \
+  QK_MAX_COARSE_STEPS=$st TMO=60 TAIL=1 $R/profiles/tools/run_cxx_ranks.sh 4 . $R/oracle/_ref/ref_RadBeam $R/quokka_amd/host/decks/beam.in plotfile_interval=-1 \
      checkpoint_interval=-1 amr.max_grid_size=${MGS:-32} qk.level0_distribution=${DIST:-bricks} qk.dump_state=many.bin > many.log 2>&1
   python - <<PY
 import sys, numpy as np

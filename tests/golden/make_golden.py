@@ -16,6 +16,6 @@ np.save(os.path.join(here, "sod_1024_final.npy"), s.valid()[:, 0, 0, :])
 s = o.sim(SEDOV, 3, [32] * 3, [0, 0, 0], [1.2] * 3, [0, 0, 0])
 for _ in range(10):
     assert s.step()
-np.save(os.path.join(here, "sedov_32_step10.npy"), s.valid(0))
+np.savez_compressed(os.path.join(here, "sedov_32_step10.npz"), state=s.valid(0))  # (compressed: 1.5 MB as .npy)
 # ghost-filled Sedov state with a developed shock: input vector for the per-operator GPU parity tests
-np.save(os.path.join(here, "sedov_32_step10_ghosted.npy"), (s.fill_ghosts(0, s.time), s.state(0))[1])
+np.savez_compressed(os.path.join(here, "sedov_32_step10_ghosted.npz"), state=(s.fill_ghosts(0, s.time), s.state(0))[1])

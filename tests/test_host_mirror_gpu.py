@@ -75,7 +75,7 @@ def test_sedov_executable_matches_golden(tmp_path, handoff):
     data, meta, out = run("ref_HydroBlast3D", ["geometry.prob_lo=0 0 0", "geometry.prob_hi=1.2 1.2 1.2", "geometry.is_periodic=0 0 0",
                                                  "amr.n_cell=32 32 32", "amr.max_grid_size=32", "max_timesteps=10", f"qk.prim_handoff={handoff}"],
                           tmp_path, allow_fail=True)
-    gold = np.load(os.path.join(ROOT, "tests", "golden", "sedov_32_step10.npy"))
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "sedov_32_step10.npz"))["state"]
     assert int(meta[0]) == 10
     assert np.array_equal(data.reshape(6, 32, 32, 32), gold)
     assert "Energy conservation is OK." in out

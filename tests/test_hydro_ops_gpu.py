@@ -97,7 +97,7 @@ def test_flux_pipeline_bit_exact_random_3d(ctx, oracle, reconstruct_eint, order)
 
 def test_flux_pipeline_bit_exact_on_sedov_state(ctx, oracle):
     """Golden ghost-filled Sedov state after 10 steps (E_int floor path, strong blast)."""
-    U = np.load(os.path.join(HERE, "golden", "sedov_32_step10_ghosted.npy"))
+    U = np.load(os.path.join(HERE, "golden", "sedov_32_step10_ghosted.npz"))["state"]
     vlo, vhi = [0, 0, 0], [31, 31, 31]
     to, tg = pyoracle.traits(1.4, False, 3), capi.traits(1.4, False, 3)
     for order in (3, 0):

@@ -94,7 +94,7 @@ def test_sedov_conservation_symmetry_and_box_invariance(oracle):
     # octant symmetry x <-> y (exact for rho; momenta swap)
     assert np.abs(U1[0] - U1[0].transpose(0, 2, 1)).max() <= 1e-15
     assert np.abs(U1[1] - U1[2].transpose(0, 2, 1)).max() <= 1e-15
-    gold = np.load(os.path.join(HERE, "golden", "sedov_32_step10.npy"))
+    gold = np.load(os.path.join(HERE, "golden", "sedov_32_step10.npz"))["state"]
     assert np.array_equal(gold, U1)
 
 

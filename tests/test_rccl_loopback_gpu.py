@@ -12,6 +12,7 @@ import sys
 
 import numpy as np
 import pytest
+from test_reference_problems_gpu import exe
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -82,7 +83,7 @@ def _run_exe(name, args, tmp_path, tag, loopback):
     env.pop("QK_GHOST_LOOPBACK", None)
     if loopback:
         env["QK_GHOST_LOOPBACK"] = "1"
-    p = subprocess.run([os.path.join(HOST, "bin", name)] + args + [f"qk.dump_state={dump}"], capture_output=True, text=True, timeout=900, env=env,
+    p = subprocess.run([exe(name)] + args + [f"qk.dump_state={dump}"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(tmp_path))
     # (the exit status is the problem's own verdict on its END state — HydroBlast3D compares with the Sedov solution —, not asked for after a dozen steps)
     assert "Performance figure-of-merit" in p.stdout and os.path.exists(dump), p.stdout[-2000:] + p.stderr[-2000:]

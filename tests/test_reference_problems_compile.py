@@ -58,10 +58,10 @@ def test_reference_problem_files_compile_unchanged():
 def test_unmodified_ode_integration_problem_passes_on_the_host():
     """src/problems/ODEIntegration/test_ode.cpp, unchanged, against the host mirror's adaptive RK integrator (host/compat/ode_integrate.hpp) and
     gamma-law quokka::EOS: a cooling gas integrated over ten cooling times must end within 1e-4 of T = 160.526 K.  Host code only — no GPU —, so
-    this runs wherever the binary was built (bin/ref_ODEIntegration; __graft_entry__.build() builds it where the reference tree exists)."""
-    exe = os.path.join(HOST, "bin", "ref_ODEIntegration")
+    this runs wherever the binary was built (oracle/_ref/ref_ODEIntegration; __graft_entry__.build() builds it where the reference tree exists)."""
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_ODEIntegration")
     if not os.path.exists(exe):
-        pytest.skip("bin/ref_ODEIntegration not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/ref_ODEIntegration not built (needs the reference tree at build time)")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-500:]
     m = re.search(r"Relative error: ([0-9.eE+-]+)", p.stdout)

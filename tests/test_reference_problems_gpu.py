@@ -1,8 +1,8 @@
 """The reference's OWN problem files — read in place from /root/reference/src/problems, compiled UNCHANGED against quokka_amd/host
-(`make -C quokka_amd/host refproblems`: -x hip; their ParallelFor / MFIter lambdas, setCustomBoundaryConditions and
+(oracle/Makefile refproblem, into oracle/_ref/: -x hip; their ParallelFor / MFIter lambdas, setCustomBoundaryConditions and
 ErrorEst run as HIP kernels, every hot-path operator goes through the C-ABI) — run on the GPU with the reference's decks and meet the
-reference's own pass criteria.  The binaries are built in the build container (where the reference tree exists) and travel to the GPU
-box with quokka_amd/host/bin/MANIFEST; the sources do not.  A binary the MANIFEST lists but that is missing is a FAILURE; the module
+reference's own pass criteria.  The binaries are built where the reference tree exists and travel to the GPU machine with
+oracle/_ref/MANIFEST; the sources do not.  A binary the MANIFEST lists but that is missing is a FAILURE; the module
 skips only where nothing was ever built (no MANIFEST)."""
 import os
 import re
@@ -15,15 +15,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "quokka_amd", "host")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 def exe(name):
-    path = os.path.join(HOST, "bin", name)
+    path = os.path.join(REF_BIN, name)
     if not os.path.exists(path):
-        manifest = os.path.join(HOST, "bin", "MANIFEST")
+        manifest = os.path.join(REF_BIN, "MANIFEST")
         built = open(manifest).read().split() if os.path.exists(manifest) else []
-        assert name not in built, f"{name} is listed in bin/MANIFEST but missing: the reference-problem coverage would silently be zero"
-        pytest.skip(f"{name} not built (needs the reference tree at build time: make -C quokka_amd/host refproblems)")
+        assert name not in built, f"{name} is listed in oracle/_ref/MANIFEST but missing: the reference-problem coverage would silently be zero"
+        pytest.skip(f"{name} not built (needs the reference tree at build time: __graft_entry__.build_refproblems)")
     return path
 
 
@@ -36,7 +37,7 @@ def test_unmodified_sedov_problem_matches_the_oracle_state_and_its_own_criteria(
     dump = str(tmp_path / "state.bin")
     rc, out = run([exe("ref_HydroBlast3D"), "geometry.prob_lo=0 0 0", "geometry.prob_hi=1.2 1.2 1.2", "geometry.is_periodic=0 0 0", "amr.n_cell=32 32 32",
                    "amr.max_grid_size=32", "max_timesteps=10", f"qk.dump_state={dump}"], str(tmp_path))
-    gold = np.load(os.path.join(ROOT, "tests", "golden", "sedov_32_step10.npy"))
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "sedov_32_step10.npz"))["state"]
     data = np.fromfile(dump, dtype=np.float64)
     assert np.array_equal(data.reshape(6, 32, 32, 32), gold), out[-1500:]  # the device-lambda initial conditions + fused path == oracle, bit for bit
     assert "Energy conservation is OK." in out
