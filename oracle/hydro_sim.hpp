@@ -408,6 +408,87 @@ struct HydroSim {
 		}
 	}
 
+	// The carried form of the RK2 average (rk2_carry_rhs): this project's design, not the reference's — a restatement of the GPU kernel's formula
+	// (quokka_amd/csrc/qk_hydro_fused.hip, header and updateCellFrom with CS = 1 / 2), so that the kernels that run in this form can be held to
+	// every bit.  Stage 1's first pass stores per cell S = U_old + (dt/2) r_1 (r_1 with its P dV term; the scalars have none) and P(U_old);
+	// stage 2 finishes U_new = S + (dt/2) r_2, r_2 from stage 2's OWN fluxes and face velocities with the P dV term on the stored pressure.
+	// U_old + dt (r_1 + r_2) / 2 in exact arithmetic: within rounding of the reference's flux_rk2 = 0.5 F1 + 0.5 F2.
+	// A stage-1 correction leaves S as the first pass stored it (uncorrected r_1); a stage 2 whose carried pass flags cells is redone in the
+	// exact form from flux_rk2 (its own first pass, then its correction), which is why flux_rk2 / avgFaceVel are still accumulated.
+	bool rk2_carry_rhs = false;
+	long carry2_fallbacks = 0; // stages 2 of the carried form redone in the exact form
+	MultiFab carryHalf_; // S (nc components) and P(U_old) of the last stage 1, read by stage 2 (and by the tests: orc_sim_carry_half)
+
+	// stage 1: S and P(U_old) into `half` (nc + 1 components) from the first pass's right-hand side (operand order of updateCellFrom, CS = 1)
+	void carryStore(MultiFab &half, MultiFab const &rhs, MultiFab const &stateOld, double dt_lev) const
+	{
+		const int nc = ncompHydro();
+		const double hdt = 0.5 * dt_lev;
+		auto const tasks = slabTasks(half.size(), [&](int b) { return grids[b]; }, ndim());
+		_Pragma("omp parallel for schedule(dynamic)")
+		for (size_t t = 0; t < tasks.size(); ++t) {
+			int const b = tasks[t].first;
+			Box const &r = tasks[t].second;
+			auto h = half.array(b);
+			auto R = rhs.const_array(b);
+			auto U = stateOld.const_array(b);
+			for (int k = r.lo[2]; k <= r.hi[2]; ++k) {
+				for (int j = r.lo[1]; j <= r.hi[1]; ++j) {
+					for (int i = r.lo[0]; i <= r.hi[0]; ++i) {
+						for (int n = 0; n < nc; ++n) {
+							h(i, j, k, n) = U(i, j, k, n) + hdt * R(i, j, k, n);
+						}
+						h(i, j, k, nc) = hydro.ComputePressure(U, i, j, k);
+					}
+				}
+			}
+		}
+	}
+
+	// stage 2, carried pass: r_2 = ComputeRhsFromFluxes(F2) - P_stored div v2, stateNew = S + (dt/2) r_2, validity flag as PredictStep
+	void rhsPdvCarried(MultiFab &rhs, FluxArrays const &fluxes, FluxArrays const &faceVel, MultiFab const &half, MultiFab &stateNew, double dt_lev,
+			   iMultiFab &redoFlag) const
+	{
+		const int nc = ncompHydro();
+		const double hdt = 0.5 * dt_lev;
+		auto const tasks = slabTasks(rhs.size(), [&](int b) { return grids[b]; }, ndim());
+		_Pragma("omp parallel for schedule(dynamic)")
+		for (size_t t = 0; t < tasks.size(); ++t) {
+			int const b = tasks[t].first;
+			std::array<Array4<const double>, 3> f{}, v{};
+			for (int d = 0; d < ndim(); ++d) {
+				f[d] = fluxes[d].const_array(b);
+				v[d] = faceVel[d].const_array(b);
+			}
+			Box const &r = tasks[t].second;
+			hydro.ComputeRhsFromFluxes(rhs.array(b), f, geom.dx, nc, r);
+			auto R = rhs.array(b);
+			auto h = half.const_array(b);
+			auto Un = stateNew.array(b);
+			auto flag = redoFlag.array(b);
+			Array4<const double> cn(Un.p, Un.box(), Un.ncomp);
+			for (int k = r.lo[2]; k <= r.hi[2]; ++k) {
+				for (int j = r.lo[1]; j <= r.hi[1]; ++j) {
+					for (int i = r.lo[0]; i <= r.hi[0]; ++i) {
+						// (AddInternalEnergyPdV, the branch of an unflagged cell, on the stored pressure)
+						double div_v = (v[0](i + 1, j, k) - v[0](i, j, k)) / geom.dx[0];
+						if (ndim() >= 2) {
+							div_v = div_v + (v[1](i, j + 1, k) - v[1](i, j, k)) / geom.dx[1];
+						}
+						if (ndim() == 3) {
+							div_v = div_v + (v[2](i, j, k + 1) - v[2](i, j, k)) / geom.dx[2];
+						}
+						R(i, j, k, internalEnergy_index) += -h(i, j, k, nc) * div_v;
+						for (int n = 0; n < nc; ++n) {
+							Un(i, j, k, n) = h(i, j, k, n) + hdt * R(i, j, k, n);
+						}
+						flag(i, j, k) = hydro.isStateValid(cn, i, j, k) ? redo_none : redo_redo;
+					}
+				}
+			}
+		}
+	}
+
 	void limitsAndSync(MultiFab &state) const
 	{
 		auto const tasks = slabTasks(state.size(), [&](int b) { return grids[b]; }, ndim());
@@ -506,8 +587,14 @@ struct HydroSim {
 		}
 		MultiFab &state_inter_cc_ = pooled ? *pool_.inter : *localInter;
 		// whole stages box by box (fusedStage) where the fused flux evaluation applies and the state is the six hydro variables
-		const bool stagesFused = pooled && use_fused_stages && state_old_cc_tmp.ng == 4 && ncomp_cc == nc && nc == 6 &&
+		// the carried form of the RK2 average where the GPU path runs it (simulation.py _carry_active: two stages, 3-D); the whole-stage leg forms
+		// the exact average only and stands aside
+		const bool carry = rk2_carry_rhs && integratorOrder_ == 2 && ndim() == 3;
+		const bool stagesFused = pooled && use_fused_stages && !carry && state_old_cc_tmp.ng == 4 && ncomp_cc == nc && nc == 6 &&
 					 fusedHydroFluxesApplicable(hydro.tr, reconstructionOrder_, is_mhd_enabled);
+		if (carry && carryHalf_.nc != nc + 1) {
+			carryHalf_ = MultiFab(grids, nc + 1, 0, ndim());
+		}
 		if (!(stagesFused && pool_.defined)) { // (a fused stage writes every valid cell and the ghost fill the same ghost cells every step: what is
 						       //  never written stays the zero of the first step's clear)
 			state_inter_cc_.setVal(0);
@@ -600,6 +687,9 @@ struct HydroSim {
 				rhsPdvPredict(rhs, fluxArrays, faceVel, stateOld, stateNew, dt_lev, redoFlag);
 				ncells_bad = sumFlags(redoFlag);
 			}
+			if (carry) { // (from the first pass: a correction below leaves S alone)
+				carryStore(carryHalf_, rhs, stateOld, dt_lev);
+			}
 			if (ncells_bad > 0) {
 				fofc1_cells += ncells_bad;
 				if (verbose != 0) {
@@ -667,6 +757,16 @@ struct HydroSim {
 			if (stagesFused) {
 				ProfScope const ps(this, "fused stage");
 				ncells_bad = fusedStage(2, stateInter, stateOld, stateFinal, fv2, flux_rk2, avgFaceVel, dt_lev, redoFlag);
+			} else if (carry) {
+				ProfScope const ps(this, "rhs + PdV + carried update");
+				rhsPdvCarried(rhs, fluxArrays, faceVel, carryHalf_, stateFinal, dt_lev, redoFlag);
+				ncells_bad = sumFlags(redoFlag);
+				if (ncells_bad > 0) { // the stage in the exact form: a first pass of its own (its own flags), corrected below where it flags cells
+					++carry2_fallbacks;
+					redoFlag.setVal(redo_none);
+					rhsPdvPredict(rhs, flux_rk2, avgFaceVel, stateOld, stateFinal, dt_lev, redoFlag);
+					ncells_bad = sumFlags(redoFlag);
+				}
 			} else {
 				ProfScope const ps(this, "rhs + PdV + PredictStep");
 				rhsPdvPredict(rhs, flux_rk2, avgFaceVel, stateOld, stateFinal, dt_lev, redoFlag);

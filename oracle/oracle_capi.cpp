@@ -399,6 +399,20 @@ void orc_sim_set_fused_fluxes(void *p, int on)
 	static_cast<HydroSim *>(p)->use_fused_fluxes = ((on & 1) != 0);
 	static_cast<HydroSim *>(p)->use_fused_stages = ((on & 2) != 0);
 }
+// the carried form of the RK2 average (HydroSim::rk2_carry_rhs, this project's design: the GPU kernel's formula restated); 0 (default): the reference's
+void orc_sim_set_rk2_carry_rhs(void *p, int on) { static_cast<HydroSim *>(p)->rk2_carry_rhs = (on != 0); }
+long orc_sim_carry2_fallbacks(void *p) { return static_cast<HydroSim *>(p)->carry2_fallbacks; }
+// what the last stage 1 of the carried form stored for box b, [ncomp + 1][valid cells] (S, then P(U_old)); returns the number of values, 0 before any
+long orc_sim_carry_half(void *p, int b, double *out)
+{
+	auto *s = static_cast<HydroSim *>(p);
+	if (s->carryHalf_.nc == 0) {
+		return 0;
+	}
+	auto const &d = s->carryHalf_.fabs[b].d;
+	std::copy(d.begin(), d.end(), out);
+	return static_cast<long>(d.size());
+}
 // both forms of the flux evaluation on the sim's CURRENT state_new (ghost cells filled here): flux[d] as [6][faces] + face velocity [faces], x fastest
 int orc_sim_hydro_fluxes(void *p, int fused, int b, int dir, double *flux_out, double *vel_out)
 {

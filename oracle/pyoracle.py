@@ -365,6 +365,21 @@ class OracleSim:
         self.o.lib.orc_sim_set_fused_fluxes.argtypes = [C.c_void_p, C.c_int]
         self.o.lib.orc_sim_set_fused_fluxes(self.h, (1 if on else 0) | (2 if (on and stages) else 0))
 
+    def set_rk2_carry_rhs(self, on: bool):
+        """the carried form of the RK2 average (HydroSim::rk2_carry_rhs; the GPU path's `rk2_carry_rhs`): stage 1 keeps U_old + (dt/2) r_1 and P(U_old)
+        per cell, stage 2 finishes with (dt/2) r_2 of its own fluxes.  Off by default (the reference's flux_rk2 = 0.5 F1 + 0.5 F2)."""
+        self.o.lib.orc_sim_set_rk2_carry_rhs.argtypes = [C.c_void_p, C.c_int]
+        self.o.lib.orc_sim_set_rk2_carry_rhs(self.h, int(bool(on)))
+
+    def carry_half(self, b: int = 0) -> np.ndarray:
+        """what the last stage 1 of the carried form stored for box b: (ncomp + 1, nz, ny, nx), S = U_old + (dt/2) r_1 then P(U_old)"""
+        lo, hi = self.box(b)
+        a = np.empty((self.ncomp + 1,) + tuple(hi[d] - lo[d] + 1 for d in (2, 1, 0)))
+        f = self.o.lib.orc_sim_carry_half
+        f.argtypes, f.restype = [C.c_void_p, C.c_int, C.POINTER(C.c_double)], C.c_long
+        assert f(self.h, int(b), _dp(a)) == a.size, "no carried stage 1 has run"
+        return a
+
     def hydro_fluxes(self, b: int, direction: int, fused: bool):
         """(flux[6, faces...], face velocity) of box b from the current state_new (ghost cells filled here), by either form"""
         lo, hi = self.box(b)
@@ -429,7 +444,10 @@ class OracleSim:
     def counters(self):
         out = (C.c_long * 3)()
         self.o.lib.orc_sim_counters(self.h, out)
-        return {"fofc1_cells": out[0], "fofc2_cells": out[1], "retries": out[2]}
+        f = self.o.lib.orc_sim_carry2_fallbacks
+        f.argtypes, f.restype = [C.c_void_p], C.c_long
+        # carry2_fallbacks: stages 2 of the carried form (set_rk2_carry_rhs) whose carried pass flagged cells and that were redone in the exact form
+        return {"fofc1_cells": out[0], "fofc2_cells": out[1], "retries": out[2], "carry2_fallbacks": f(self.h)}
 
 
 class OracleCloudy:

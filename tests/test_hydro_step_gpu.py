@@ -465,22 +465,27 @@ def test_carried_rhs_mode_stays_within_the_parity_tolerance(ctx, oracle, mgs):
     """qk_hydro_stage_args::rk2_carry_rhs = 1: stage 1 stores div F1 / div v1 per cell, stage 2 averages the right-hand sides instead of the face
     fluxes.  Not bit-exact by construction (different rounding of the same quantity): the contract is north_star's 1e-12 relative L1 per
     conserved component against the oracle — checked after 40 steps of the blast crossing box boundaries — and it must really be the other
-    mode (some bits differ), with the face arrays never touched."""
+    mode (some bits differ), with the face arrays never touched.  Against the oracle's own carried form (set_rk2_carry_rhs): every bit and every dt."""
     N, nsteps = 32, 40
     so = oracle.sim(SEDOV, 3, [N] * 3, [0, 0, 0], [1.2] * 3, [0, 0, 0], max_grid_size=[mgs] * 3)
+    sc = oracle.sim(SEDOV, 3, [N] * 3, [0, 0, 0], [1.2] * 3, [0, 0, 0], max_grid_size=[mgs] * 3)
+    sc.set_rk2_carry_rhs(True)
     sg = sedov_problem(ctx, N, max_grid_size=mgs)
     sg.rk2_carry_rhs = True
     for d in range(3):
         sg.halfFlux[d].storage.fill_(float("nan"))  # a read of F1 would poison the state
     for it in range(nsteps):
-        assert so.step() and sg.step()
+        assert so.step() and sg.step() and sc.step()
         assert abs(so.dt - sg.dt_) <= 1e-13 * so.dt, f"dt at step {it}: {so.dt} vs {sg.dt_}"
+        assert sc.dt == sg.dt_, f"dt at step {it}: {sc.dt} (carried oracle) vs {sg.dt_}"
     Uo, Ug = gather_oracle(so, N), gather_gpu(sg, N)
     assert np.isfinite(Ug).all()
     err = rel_l1(Ug, Uo)
     print(f"carried-rhs mode vs oracle after {nsteps} steps ({mgs}^3 boxes): relative L1 = {err:.3e}")
     assert err <= 1e-12
     assert not np.array_equal(Uo, Ug)
+    Uc = gather_oracle(sc, N)
+    assert np.array_equal(Uc, Ug), f"carried oracle: {int((Uc != Ug).sum())} values differ, max abs diff {np.abs(Uc - Ug).max()}"
     assert all(bool(torch.isnan(sg.halfFlux[d].storage).all()) for d in range(3))
     assert sg.counters["fofc1_stages"] + sg.counters["fofc2_stages"] == 0
 
@@ -489,15 +494,19 @@ def test_carried_rhs_mode_with_first_order_flux_correction(ctx, oracle):
     """the carried mode when the fused stages flag cells: stage 1 takes the fused correction pass; stage 2 — whose correction replaces
     flux_rk2 = 0.5 F1 + 0.5 F2 of a face as a whole, with F1 never stored in this mode — is redone in the exact form on the FUSED kernels (F1
     from one more run of the stage-1 sweeps over the old state).  No reference-shaped operator runs.  Same over-CFL step as
-    test_fofc_and_retries_match_oracle."""
+    test_fofc_and_retries_match_oracle.  Every bit of the oracle's own carried form (set_rk2_carry_rhs), which takes the same stage-1 correction,
+    exact-form stage 2 and retries."""
     N, mgs = 16, 8
     so = oracle.sim(SEDOV, 3, [N] * 3, [0, 0, 0], [1.2] * 3, [0, 0, 0], max_grid_size=[mgs] * 3)
+    sc = oracle.sim(SEDOV, 3, [N] * 3, [0, 0, 0], [1.2] * 3, [0, 0, 0], max_grid_size=[mgs] * 3)
+    sc.set_rk2_carry_rhs(True)
     sg = sedov_problem(ctx, N, max_grid_size=mgs)
     sg.rk2_carry_rhs = True
     for _ in range(3):
-        assert so.step() and sg.step()
+        assert so.step() and sg.step() and sc.step()
+        assert sc.dt == sg.dt_
     dt = so.compute_dt() * 6.0
-    assert so.advance_fixed_dt(dt)
+    assert so.advance_fixed_dt(dt) and sc.advance_fixed_dt(dt)
     def no_operators(*a, **k):
         raise AssertionError("a stage fell back to the reference-shaped operators")
     sg._redo_stage_unfused = no_operators
@@ -506,6 +515,9 @@ def test_carried_rhs_mode_with_first_order_flux_correction(ctx, oracle):
     assert sg.counters["retries"] == co["retries"] and sg.counters["fofc1_stages"] > 0 and sg.counters["fofc2_stages"] > 0
     assert sg._unfused_tmp is None  # (the operator path's temporaries were never even allocated)
     assert rel_l1(gather_gpu(sg, N), gather_oracle(so, N)) <= 1e-12
+    cc = sc.counters()
+    assert cc["retries"] == co["retries"] and cc["fofc1_cells"] > 0 and cc["carry2_fallbacks"] > 0, cc
+    assert np.array_equal(gather_oracle(sc, N), gather_gpu(sg, N))
 
 
 def test_drift_of_the_carried_form_is_that_of_a_one_ulp_perturbation(ctx):
