@@ -1,10 +1,12 @@
-// qk_hydro_fused.hip — the throughput path: one RK stage of the hydro update as FOUR launches over all boxes of a level
+// qk_hydro_fused.hip — the throughput path: one RK stage of the hydro update as a pre-pass and up to three sweeps over all boxes of a level
 //   k_pre3           U -> the combined flattening coefficient of FlattenShocks [ComputeFlatteningCoefficients<X1,X2,X3> + FlattenShocks]
 //                    and the velocity differences D_x, D_y, D_z of the carbuncle switch, on valid + 1: x-y tile + march along z
 //   k_sweep_x        PPM (or PLM / donor) reconstruction + shock flattening + HLLC + flux divergence + face-velocity divergence along x:
 //                    one thread per cell of a row-contiguous slab, +-2 stencil, edge states and fluxes through LDS
 //   k_sweep_march<Y> the same along y: lanes along x, each thread marches along y with a 5-cell primitive window in registers
 //   k_sweep_march<Z> the same along z + the epilogue: P dV term, PredictStep, validity flag, EnforceLimits, SyncDualEnergy, CFL maxima
+// Four launches — or three: on a 3-D level in the carried form (no flux mask, no passive scalars, boxes whole waves wide) the X sweep rides inside
+// the Y march (FUSEX, profile label k_sweep_xy) and k_sweep_x is not launched; QK_FUSEX=0 selects the four-launch path.
 // Every sweep converts U to primitives itself (no primitive arrays in HBM); a 7-double right-hand-side accumulator travels X -> Y -> Z.
 // Two ways to form the RK2 average (qk_hydro_stage_args::rk2_carry_rhs):
 //   0  the reference's: flux_rk2 = 0.5 F1 + 0.5 F2 face by face — stage 1 stores F1 (7 doubles per face and direction), stage 2 reads
@@ -18,7 +20,9 @@
 // All arithmetic lives in qk_device.hpp, shared with the reference-shaped operators -> identical bits.
 #include "qk_device.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "qk_internal.hpp"
@@ -33,26 +37,9 @@ constexpr int NG = 4; // nghost_cc_ (reference src/simulation.hpp:363)
 // Non-temporal hints on the streams a launch touches exactly once: the stores of the flux-divergence accumulator (X, Y), of the new state and of the
 // carried half step (final sweep), and the loads of the accumulator (Y, final sweep).  Measured same-box (profiles/round4/ab12_*): Z -1.3 ... -1.5 %,
 // Y -1 %, 512^3 headline +1.6 %.  Not on the state reads (neighbouring lanes and sweeps share their lines) and not on the pre-pass's outputs
-// (measured: the pre-pass 5 - 8 % slower with them).  QK_NT=0: no hints, 1: stores only.
-#ifndef QK_NT
-#define QK_NT 2
-#endif
-template <class P> QK_DEV void streamStore(P *p, double v)
-{
-#if QK_NT >= 1
-	__builtin_nontemporal_store(v, p);
-#else
-	*p = v;
-#endif
-}
-template <class P> QK_DEV auto streamLoad(P *p) -> double
-{
-#if QK_NT >= 2
-	return __builtin_nontemporal_load(p);
-#else
-	return *p;
-#endif
-}
+// (measured: the pre-pass 5 - 8 % slower with them).
+template <class P> QK_DEV void streamStore(P *p, double v) { __builtin_nontemporal_store(v, p); }
+template <class P> QK_DEV auto streamLoad(P *p) -> double { return __builtin_nontemporal_load(p); }
 
 // geometry of the ghost-4 scratch fab of one box
 struct SGeom {
@@ -197,24 +184,13 @@ QK_DEV auto chiCompressive(double Pm2, double Pm1, double Pp1, double Pp2, Recip
 // of a tile are then found in the L2 of the XCD that just read them for the tile before.
 // ndim < 3: the fab has no ghost cells in the inactive dimensions — rows / planes outside it take the neutral state and the flattening coefficient of
 // an inactive direction is 1 (FlattenShocks takes the minimum over the AMREX_SPACEDIM active directions only, hydro_system.hpp:655-669).
-// QK_PRE_PREFETCH (A/B knob, default 0): the next plane's values requested one plane ahead — 1 in both stages, 2 only in the stage that reads
-// primitives (whose conversion-free body needs 112 registers instead of 118).  Measured in round 5 (profiles/round5/ab6_pre_prefetch.txt): the 20
-// registers of the two in-flight cells spill 24 / 80 bytes per lane under the 128-register cap: 0.39 -> 0.42 ms (2), -> 0.53 ms (1) per launch.
-#ifndef QK_PRE_PREFETCH
-#define QK_PRE_PREFETCH 0
-#endif
-#ifndef QK_MARCH_PREFETCH
-#define QK_MARCH_PREFETCH 1
-#endif
-#ifndef QK_PRE_HALO_DIET
-#define QK_PRE_HALO_DIET 1 // (A/B knob)
-#endif
+// (Requesting the next plane's values one plane ahead was measured and rejected in round 5, profiles/round5/ab6_pre_prefetch.txt: the 20 registers of
+// the two in-flight cells spill under the 128-register cap, 0.39 -> 0.42 ... 0.53 ms per launch — the kernel is issue-bound, not latency-bound.)
 template <bool PRIM>
 __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, const SGeom *geom, const qk_array4 *U_t, double *scratch, int64_t T, Eos eos, bool re, int nseg,
 							    int xt, int yt, int ndim)
 {
 	constexpr bool prim_in = PRIM;
-	constexpr bool PF = (QK_PRE_PREFETCH == 1) || (QK_PRE_PREFETCH == 2 && PRIM); // the next plane's values requested one plane ahead
 	const unsigned nblk = gridDim.x, lin = blockIdx.x;
 	const unsigned q8 = nblk / 8, r8 = nblk % 8, xcd = lin % 8, slot = lin / 8;
 	const unsigned logical = (xcd < r8) ? xcd * (q8 + 1) + slot : r8 * (q8 + 1) + (xcd - r8) * q8 + slot;
@@ -281,35 +257,16 @@ __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, con
 	const Recip Rbeta = recipOf(0.85 - 0.75); // beta_max - beta_min (hydro_system.hpp:596-597, :609)
 	double fm[4] = {1., 1., 1., 1.}, fdx[4] = {0., 0., 0., 0.}, fdy[4] = {0., 0., 0., 0.}; // in-plane results of planes k-3 .. k
 	double *Sout = scratch + g.off;
-	// (requesting the next plane's conserved values one plane ahead was measured: +20 registers, spills under the 128-register cap that two
-	// workgroups per CU need, 15 % slower — the kernel is issue-bound, not latency-bound)
 	const PlaneRaw neutral{1., 0., 0., 0., prim_in ? 1. : 1. / eos.gm1};
 	// prim_in: the array holds (rho, v_x, v_y, v_z, P, E_int) — what planeCell would form (stage 2 after a stage 1 with prim_out)
 	auto cellOf = [&](PlaneRaw const &r) -> PlaneCell { return prim_in ? PlaneCell{r.rho, r.mx, r.my, r.mz, r.E} : planeCell(eos, re, r); };
 	int64_t uo = ownIn ? U.idx(oi, oj, zfirst - 3) : 0;
 	int64_t uh = haloIn ? U.idx(hi_, hj, zfirst - 3) : 0;
-	PlaneRaw nextOwn = neutral, nextHalo = neutral;
-	if constexpr (PF) {
-		const bool k0In = (zfirst - 3 >= fzlo) && (zfirst - 3 <= fzhi);
-		nextOwn = (ownIn && k0In) ? planeLoad(U, uo) : neutral;
-		nextHalo = (haloIn && k0In && (zfirst - 3 >= zfirst)) ? planeLoad(U, uh) : neutral;
-	}
 
 	for (int k = zfirst - 3; k <= zlast + 3; ++k, uo += U.ks, uh += U.ks) {
 		const bool inPlane = (k >= zfirst) && (k <= zlast); // uniform: this plane's x / y results are somebody's output
 		const bool kIn = (k >= fzlo) && (k <= fzhi);	      // uniform: the plane exists in the fab
-		PlaneRaw rawOwn, rawHalo = neutral;
-		if constexpr (PF) {
-			rawOwn = nextOwn;
-			rawHalo = nextHalo;
-			const int kn = k + 1;
-			const bool knIn = (kn >= fzlo) && (kn <= fzhi) && (kn <= zlast + 3);
-			nextOwn = (ownIn && knIn) ? planeLoad(U, uo + U.ks) : neutral;
-			nextHalo = (haloIn && knIn && (kn >= zfirst) && (kn <= zlast)) ? planeLoad(U, uh + U.ks) : neutral;
-		} else {
-			rawOwn = (ownIn && kIn) ? planeLoad(U, uo) : neutral;
-		}
-		const PlaneCell c = cellOf(rawOwn);
+		const PlaneCell c = cellOf((ownIn && kIn) ? planeLoad(U, uo) : neutral);
 #pragma unroll
 		for (int m = 0; m < 4; ++m) {
 			Pz[m] = Pz[m + 1];
@@ -336,7 +293,7 @@ __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, con
 				s_vy[ty + 2][tx] = c.vy;
 			}
 			if (h >= 0) {
-				if constexpr (PRIM && !PF && QK_PRE_HALO_DIET != 0) {
+				if constexpr (PRIM) {
 					// a halo cell of the primitive form is needed for its pressure; its v_x only in the tile's rows within two columns of the tile,
 					// its v_y only in the tile's columns within two rows, its density only on the rim (the shock-strength ratio of chi there):
 					// 2.3 loads per halo cell instead of 5 (the conserved form needs all five to form the pressure)
@@ -353,7 +310,7 @@ __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, con
 						}
 					}
 				} else {
-					hc = cellOf(PF ? rawHalo : ((haloIn && kIn) ? planeLoad(U, uh) : neutral));
+					hc = cellOf((haloIn && kIn) ? planeLoad(U, uh) : neutral);
 				}
 				s_P[hy + 3][hx + 3] = hc.P;
 				if (hy >= 0 && hy < PT_Y && hx >= -2 && hx < PT_X + 2) {
@@ -445,6 +402,80 @@ QK_DEV void flattenEdges(double chi, double mean, double &am, double &ap)
 	ap = chi * ap + (1. - chi) * mean;
 }
 
+// reconstruction + shock flattening of one variable of a cell from its +-2 neighbours: the edge states a_minus, a_plus
+template <int ORDER> QK_DEV void reconstructVar(double chi, double qm2, double qm1, double q0, double qp1, double qp2, double &am, double &ap)
+{
+	cellEdges<ORDER>(qm2, qm1, q0, qp1, qp2, am, ap);
+	flattenEdges(chi, q0, am, ap);
+}
+// ... of all NV variables of one cell: the edge states a_minus, a_plus.  nb(m, n) is variable n of the neighbour at distance
+// m = -2, -1, 1, 2 — registers of a marching window or slots of an LDS row; it is called variable by variable, so that a caller whose neighbours are in LDS
+// holds four of their values at a time, not 4 NV (the fused XY sweep has no registers to spare).
+template <int ORDER, int NV, class NB> QK_DEV void reconstructCell(double chi, const double (&q0)[NV], NB nb, double (&am)[NV], double (&ap)[NV])
+{
+#pragma unroll
+	for (int n = 0; n < NV; ++n) {
+		reconstructVar<ORDER>(chi, nb(-2, n), nb(-1, n), q0[n], nb(1, n), nb(2, n), am[n], ap[n]);
+	}
+}
+
+// the NV values a lane keeps in (reads from) slot t of a [variable][slot] LDS buffer
+template <int NV, int W> QK_DEV void getColumn(const double (*s)[W], int t, double (&v)[NV])
+{
+#pragma unroll
+	for (int n = 0; n < NV; ++n) {
+		v[n] = s[n][t];
+	}
+}
+template <int NV, int W> QK_DEV void putColumn(double (*s)[W], int t, const double (&v)[NV])
+{
+#pragma unroll
+	for (int n = 0; n < NV; ++n) {
+		s[n][t] = v[n];
+	}
+}
+
+// hydro_system.hpp:138-196: the hydro variables Uc of a cell (as loaded from U at offset u) -> primitives; prim_in (uniform): the array holds the
+// primitives already.  The passive scalars are reconstructed as they are stored (:340-343).
+template <int NS> QK_DEV void primsOf(RA4 const &U, int64_t u, Eos const &eos, bool re, bool prim_in, const double (&Uc)[NVAR], double (&q)[NVAR + NS])
+{
+	if (prim_in) {
+#pragma unroll
+		for (int n = 0; n < NVAR; ++n) {
+			q[n] = Uc[n];
+		}
+	} else {
+		consToPrim(eos, re, Uc, q);
+	}
+#pragma unroll
+	for (int n = NVAR; n < NVAR + NS; ++n) {
+		q[n] = U.p[u + U.ns * n];
+	}
+}
+// ... of the cell at offset u of U; Uc returns its hydro variables as stored
+template <int NS> QK_DEV void loadPrims(RA4 const &U, int64_t u, Eos const &eos, bool re, bool prim_in, double (&q)[NVAR + NS], double (&Uc)[NVAR])
+{
+#pragma unroll
+	for (int n = 0; n < NVAR; ++n) {
+		Uc[n] = U.p[u + U.ns * n];
+	}
+	primsOf<NS>(U, u, eos, re, prim_in, Uc, q);
+}
+
+// the flux of all NV variables through one face and the face velocity: Riemann solve of the hydro variables (faceFlux) + the passive scalars riding on
+// its waves (hydro_system.hpp:1062-1076, HLLC.hpp:126-136)
+template <int DIR, int RIEMANN, bool TWOD, int NS>
+QK_DEV void faceFluxAll(Eos const &eos, bool re, int ndim, const double (&qL)[NVAR + NS], const double (&qR)[NVAR + NS], double du, double dvl, double dvr, double dwl,
+			double dwr, double K_visc, double (&F)[NVAR + NS], double &vf)
+{
+	Wave wv;
+	faceFlux<DIR, RIEMANN, TWOD>(eos, re, ndim, qL, qR, du, dvl, dvr, dwl, dwr, K_visc, F, vf, NS > 0 ? &wv : nullptr);
+#pragma unroll
+	for (int n = NVAR; n < NVAR + NS; ++n) {
+		F[n] = scalarFlux<RIEMANN>(wv, qL[n], qR[n]);
+	}
+}
+
 // The carried form on a level that has refined children (qk_hydro_stage_args::flux_mask): the flux registers of the hierarchy need flux_rk2 = 0.5 F1 +
 // 0.5 F2 on the coarse-fine faces — a few thousand faces of 50 million.  A face with a marked cell on either side keeps F1 in halfFlux (stage 1) and
 // gets flux_rk2 written to rk2Flux (stage 2), exactly the values the reference's form stores on EVERY face; the cell updates stay carried.
@@ -488,28 +519,99 @@ template <int STAGE, int NV> QK_DEV void maskedFaceFlux(SweepArgs const &a, int 
 // counts the cells that are still invalid and writes no flags (they are its input).  Same device functions as the reference-shaped operators: the
 // result equals the operator path bit for bit.  Not instantiated for the carried-rhs form (its stage 2 has no F1 to average at the other faces) and
 // only taken for K_visc == 0 (the viscosity term of a first-order face needs the transverse differences of the old state).
-template <int NS> QK_DEV void primOfCell(RA4 const &U, Eos const &eos, bool re, int i, int j, int k, double q[NVAR + NS])
+// What becomes of the flux F (and face velocity vf) of face fi — between the cells fm = fi - 1 and fi along DIR — in this stage and form:
+//   carried form     neither stage touches the face arrays, except on the marked faces of a level with refined children (maskedFaceFlux);
+//   exact, stage 1   halfFlux / halfVel receive F1 (in the FOFC pass they keep the UNCORRECTED flux the first pass stored: flux_rk2 is formed from
+//                    it, QuokkaSimulation.hpp:1105-1108);
+//   exact, stage 2   flux_rk2 = (0 + 0.5 F1) + 0.5 F2 (QuokkaSimulation.hpp:1106, :1220) replaces F, and goes to rk2Flux on request (never over F1:
+//                    tile-boundary faces of the x sweep are evaluated twice);
+//   FOFC pass        a face that touches a cell the first pass flagged (redoFlag carries one filled ghost cell) takes the first-order flux of the old
+//                    state instead — replaceFluxes (QuokkaSimulation.hpp:1324-1368), in stage 2 flux_rk2 of the face as a whole.  In stage 1 the old
+//                    state is the input state and the caller holds its primitives (qLo, qRo); stage 2 converts the two cells of U_old.
+// The caller supplies what differs between the sweeps: `live` (the lane owns this face: stores allowed), `marked` (carried form: a cell of the face is in
+// the flux mask), F1 (exact form, stage 2: halfFlux and halfVel of the face, requested where the caller can afford the round trip).
+template <int NV> QK_DEV void loadF1(SweepArgs const &a, int b, const int (&fi)[3], double (&F1)[NV + 1])
 {
-	const int64_t u = U.idx(i, j, k);
-	double Uc[NVAR];
+	RA4 HF(a.halfFlux[b]);
+	RA4 HV(a.halfVel[b]);
+	const int64_t o = HF.idx(fi[0], fi[1], fi[2]);
 #pragma unroll
-	for (int n = 0; n < NVAR; ++n) {
-		Uc[n] = U.p[u + U.ns * n];
+	for (int n = 0; n < NV; ++n) {
+		F1[n] = HF.p[o + HF.ns * n];
 	}
-	consToPrim(eos, re, Uc, q);
+	F1[NV] = HV(fi[0], fi[1], fi[2]);
+}
+template <int STAGE, bool CARRY, bool FOFC, int DIR, int NS, bool TWOD>
+QK_DEV void settleFace(SweepArgs const &a, Eos const &eos, int ndim, int b, const int (&fi)[3], bool live, bool marked, const double (&F1)[NVAR + NS + 1],
+		       const double (&qLo)[NVAR + NS], const double (&qRo)[NVAR + NS], double (&F)[NVAR + NS], double &vf)
+{
+	constexpr int NV = NVAR + NS;
+	if (CARRY) {
+		if (marked) {
+			maskedFaceFlux<STAGE, NV>(a, b, fi[0], fi[1], fi[2], F);
+		}
+		return;
+	}
+	int fm[3] = {fi[0], fi[1], fi[2]}; // the cell on the low side of the face
+	fm[DIR] -= 1;
+	bool firstOrder = false;
+	if constexpr (FOFC) {
+		CIA4 flag(a.redoFlag[b]);
+		firstOrder = (flag(fm[0], fm[1], fm[2]) != 0) || (flag(fi[0], fi[1], fi[2]) != 0);
+	}
+	if (STAGE == 2) {
 #pragma unroll
-	for (int n = NVAR; n < NVAR + NS; ++n) {
-		q[n] = U.p[u + U.ns * n];
+		for (int n = 0; n < NV; ++n) {
+			F[n] = 0.5 * F1[n] + 0.5 * F[n];
+		}
+		vf = 0.5 * F1[NV] + 0.5 * vf;
+	}
+	if constexpr (FOFC) {
+		if (firstOrder) {
+			// computeFOHydroFluxes (QuokkaSimulation.hpp:1520-1568) for this face, on demand: donor-cell states + LLF
+			if (STAGE == 1) {
+				faceFluxAll<DIR, QK_RIEMANN_LLF, TWOD, NS>(eos, a.reconstruct_eint, ndim, qLo, qRo, 0., 0., 0., 0., 0., 0., F, vf);
+			} else {
+				RA4 Uold(a.U_old[b]);
+				double qL[NV], qR[NV], Uc[NVAR];
+				loadPrims<NS>(Uold, Uold.idx(fm[0], fm[1], fm[2]), eos, a.reconstruct_eint, false, qL, Uc);
+				loadPrims<NS>(Uold, Uold.idx(fi[0], fi[1], fi[2]), eos, a.reconstruct_eint, false, qR, Uc);
+				faceFluxAll<DIR, QK_RIEMANN_LLF, TWOD, NS>(eos, a.reconstruct_eint, ndim, qL, qR, 0., 0., 0., 0., 0., 0., F, vf);
+			}
+		}
+	} else if (STAGE == 1) {
+		if (live) {
+			WA4 HF(a.halfFlux[b]);
+			WA4 HV(a.halfVel[b]);
+			const int64_t o = HF.idx(fi[0], fi[1], fi[2]);
+#pragma unroll
+			for (int n = 0; n < NV; ++n) {
+				HF.p[o + HF.ns * n] = F[n];
+			}
+			HV(fi[0], fi[1], fi[2]) = vf;
+		}
+	}
+	if (STAGE == 2 && a.store_rk2 && live) {
+		WA4 RF(a.rk2Flux[b]);
+		const int64_t o2 = RF.idx(fi[0], fi[1], fi[2]);
+#pragma unroll
+		for (int n = 0; n < NV; ++n) {
+			RF.p[o2 + RF.ns * n] = F[n];
+		}
 	}
 }
-template <int DIR, int NS, bool TWOD, int NDIM>
-QK_DEV void firstOrderFlux(Eos const &eos, bool re, const double qL[NVAR + NS], const double qR[NVAR + NS], double F[NVAR + NS], double &vf)
+
+// the wave's maxima of the two CFL signal speeds -> one atomic per wave and speed (max is exact, so the result is deterministic).  Every lane of the
+// wave takes part.
+QK_DEV void reduceSignal(double *max_signal, double sig0, double sig1)
 {
-	Wave wv;
-	faceFlux<DIR, QK_RIEMANN_LLF, TWOD>(eos, re, NDIM, qL, qR, 0., 0., 0., 0., 0., 0., F, vf, NS > 0 ? &wv : nullptr);
-#pragma unroll
-	for (int n = NVAR; n < NVAR + NS; ++n) {
-		F[n] = scalarFlux<QK_RIEMANN_LLF>(wv, qL[n], qR[n]);
+	for (int off = 32; off > 0; off >>= 1) {
+		sig0 = smax(sig0, __shfl_xor(sig0, off));
+		sig1 = smax(sig1, __shfl_xor(sig1, off));
+	}
+	if ((threadIdx.x & 63) == 0) {
+		atomicMaxNonNeg(&max_signal[0], sig0);
+		atomicMaxNonNeg(&max_signal[1], sig1);
 	}
 }
 // hydro_system.hpp:804-808: 0.5 * sum_d (v_d(+1) - v_d(-1)) / dx_d from the conserved variables (ComputeVelocityX1..3)
@@ -767,32 +869,12 @@ template <int ORDER, int STAGE, int NS, bool CARRY, int NDIM = 3, bool FOFC = fa
 
 	const double *S = a.scratch + g.off;
 	const int64_t T = a.total_cells;
-	double q0[NV];
+	double q0[NV], Uc[NVAR];
 	{
 		RA4 U(a.U_in[b]);
-		const int64_t u = U.idx(i, j, k);
-		double Uc[NVAR];
-#pragma unroll
-		for (int n = 0; n < NVAR; ++n) {
-			Uc[n] = U.p[u + U.ns * n];
-		}
-		if (a.prim_in) { // (uniform) the input array holds the primitives
-#pragma unroll
-			for (int n = 0; n < NVAR; ++n) {
-				q0[n] = Uc[n];
-			}
-		} else {
-			consToPrim(eos, a.reconstruct_eint, Uc, q0);
-		}
-#pragma unroll
-		for (int n = NVAR; n < NV; ++n) { // hydro_system.hpp:340-343: passive scalars are reconstructed as they are stored
-			q0[n] = U.p[u + U.ns * n];
-		}
+		loadPrims<NS>(U, U.idx(i, j, k), eos, a.reconstruct_eint, a.prim_in, q0, Uc);
 	}
-#pragma unroll
-	for (int n = 0; n < NV; ++n) {
-		s_q[n][t] = q0[n];
-	}
+	putColumn(s_q, t, q0);
 	const double chi = S[(S_AUX + 0) * T + c];
 	const double dV = S[(S_AUX + 2) * T + c]; // view-j axis of X1 is y
 	const double dW = S[(S_AUX + 3) * T + c]; // view-k axis is z
@@ -802,111 +884,40 @@ template <int ORDER, int STAGE, int NS, bool CARRY, int NDIM = 3, bool FOFC = fa
 
 	// reconstruct my cell (needs t-2 .. t+2)
 	double am[NV], ap[NV];
-	const int tm2 = max(t - 2, 0), tm1 = max(t - 1, 0), tp1 = min(t + 1, XB - 1), tp2 = min(t + 2, XB - 1);
-#pragma unroll
-	for (int n = 0; n < NV; ++n) {
-		cellEdges<ORDER>(s_q[n][tm2], s_q[n][tm1], q0[n], s_q[n][tp1], s_q[n][tp2], am[n], ap[n]);
-		flattenEdges(chi, q0[n], am[n], ap[n]);
-		s_e[n][t] = ap[n];
-	}
+	const int tm1 = max(t - 1, 0), tp1 = min(t + 1, XB - 1);
+	reconstructCell<ORDER>(chi, q0, [&](int m, int n) { return s_q[n][min(max(t + m, 0), XB - 1)]; }, am, ap);
+	putColumn(s_e, t, ap);
 	__syncthreads();
 
 	// flux at my left face
 	double qL[NV];
-#pragma unroll
-	for (int n = 0; n < NV; ++n) {
-		qL[n] = s_e[n][tm1];
-	}
+	getColumn(s_e, tm1, qL);
 	const double du = q0[PVX] - s_q[PVX][tm1];
 	const double dvl = s_d[0][tm1], dwl = s_d[1][tm1];
 	double F[NV], vf;
-	{
-		Wave wv;
-		faceFlux<0, QK_RIEMANN_HLLC>(eos, a.reconstruct_eint, NDIM, qL, am, du, dvl, dV, dwl, dW, a.K_visc, F, vf, NS > 0 ? &wv : nullptr);
-#pragma unroll
-		for (int n = NVAR; n < NV; ++n) { // hydro_system.hpp:1062-1076, HLLC.hpp:126-136
-			F[n] = scalarFlux<QK_RIEMANN_HLLC>(wv, qL[n], am[n]);
-		}
-	}
+	faceFluxAll<0, QK_RIEMANN_HLLC, false, NS>(eos, a.reconstruct_eint, NDIM, qL, am, du, dvl, dV, dwl, dW, a.K_visc, F, vf);
 
 	const bool validRow = inside;
 	const bool isFace = validRow && (i >= bx.lo[0]) && (i <= bx.hi[0] + 1) && (t >= 3) && (t <= XB - 3);
-	// FOFC pass: does this face touch a cell the first pass flagged? (redoFlag carries one filled ghost cell)
-	bool firstOrder = false;
-	if constexpr (FOFC) {
-		if (isFace) {
-			CIA4 flag(a.redoFlag[b]);
-			firstOrder = (flag(i - 1, j, k) != 0) || (flag(i, j, k) != 0);
+	if (isFace) {
+		const int fi[3] = {i, j, k};
+		double F1[NV + 1];
+		if (!CARRY && STAGE == 2) {
+			loadF1<NV>(a, b, fi, F1);
 		}
-	}
-	auto replaceByFirstOrder = [&]() { // replaceFluxes (QuokkaSimulation.hpp:1324-1368) for this face, the first-order flux evaluated on demand
-		double qLo[NV], qRo[NV];
-		if (STAGE == 1) { // the old state is the input state: its primitives are in LDS
-#pragma unroll
-			for (int n = 0; n < NV; ++n) {
-				qLo[n] = s_q[n][tm1];
-				qRo[n] = q0[n];
-			}
-		} else {
-			RA4 Uold(a.U_old[b]);
-			primOfCell<NS>(Uold, eos, a.reconstruct_eint, i - 1, j, k, qLo);
-			primOfCell<NS>(Uold, eos, a.reconstruct_eint, i, j, k, qRo);
-		}
-		firstOrderFlux<0, NS, false, NDIM>(eos, a.reconstruct_eint, qLo, qRo, F, vf);
-	};
-	if (CARRY) {
-		// carried right-hand side: neither stage touches the face arrays — except on the marked faces of a level with refined children
-		if (a.fluxMask != nullptr && isFace) {
+		bool marked = false;
+		if (CARRY && a.fluxMask != nullptr) {
 			const qk_carray4 md = a.fluxMask[b];
-			if ((maskByte(md, i - 1, j, k) | maskByte(md, i, j, k)) != 0) {
-				maskedFaceFlux<STAGE, NV>(a, b, i, j, k, F);
-			}
+			marked = (maskByte(md, i - 1, j, k) | maskByte(md, i, j, k)) != 0;
 		}
-	} else if (STAGE == 1 && FOFC) {
-		// (halfFlux keeps the UNCORRECTED stage-1 flux the first pass stored: flux_rk2 is formed from it, QuokkaSimulation.hpp:1105-1108)
-		if (firstOrder) {
-			replaceByFirstOrder();
+		double qLo[NV]; // (FOFC pass, stage 1: the old state is the input state, its primitives are in LDS)
+		if (FOFC && STAGE == 1) {
+			getColumn(s_q, tm1, qLo);
 		}
-	} else if (STAGE == 1) {
-		if (isFace) {
-			WA4 HF(a.halfFlux[b]);
-			WA4 HV(a.halfVel[b]);
-			const int64_t o = HF.idx(i, j, k);
-#pragma unroll
-			for (int n = 0; n < NV; ++n) {
-				HF.p[o + HF.ns * n] = F[n];
-			}
-			HV(i, j, k) = vf;
-		}
-	} else {
-		if (isFace) {
-			WA4 HF(a.halfFlux[b]);
-			WA4 HV(a.halfVel[b]);
-			const int64_t o = HF.idx(i, j, k);
-			// flux_rk2 = (0 + 0.5 F1) + 0.5 F2   (QuokkaSimulation.hpp:1106, :1220)
-#pragma unroll
-			for (int n = 0; n < NV; ++n) {
-				F[n] = 0.5 * HF.p[o + HF.ns * n] + 0.5 * F[n];
-			}
-			vf = 0.5 * HV(i, j, k) + 0.5 * vf;
-			if (FOFC && firstOrder) {
-				replaceByFirstOrder(); // flux_rk2 of this face as a whole
-			}
-			if (a.store_rk2) {
-				WA4 RF(a.rk2Flux[b]);
-				const int64_t o2 = RF.idx(i, j, k);
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					RF.p[o2 + RF.ns * n] = F[n];
-				}
-			}
-		}
+		settleFace<STAGE, CARRY, FOFC, 0, NS, false>(a, eos, NDIM, b, fi, true, marked, F1, qLo, q0, F, vf);
 	}
 	__syncthreads(); // everyone is done with s_q (primitives)
-#pragma unroll
-	for (int n = 0; n < NV; ++n) {
-		s_q[n][t] = F[n];
-	}
+	putColumn(s_q, t, F);
 	s_d[2][t] = vf;
 	__syncthreads();
 
@@ -941,15 +952,8 @@ template <int ORDER, int STAGE, int NS, bool CARRY, int NDIM = 3, bool FOFC = fa
 			const EpiConst ec = epiConst(eos);
 			updateCellFrom<NS, CARRY ? STAGE : 0, FOFC, 1>(a, eos, ec, b, i, j, k, Uo, rhs, div_v, r1, sig0, sig1);
 		}
-		if (a.max_signal != nullptr) { // every lane takes part in the wave reduction (no early exit above for lanes of a live workgroup)
-			for (int off = 32; off > 0; off >>= 1) {
-				sig0 = smax(sig0, __shfl_xor(sig0, off));
-				sig1 = smax(sig1, __shfl_xor(sig1, off));
-			}
-			if ((threadIdx.x & 63) == 0) {
-				atomicMaxNonNeg(&a.max_signal[0], sig0);
-				atomicMaxNonNeg(&a.max_signal[1], sig1);
-			}
+		if (a.max_signal != nullptr) { // (no early exit above for lanes of a live workgroup)
+			reduceSignal(a.max_signal, sig0, sig1);
 		}
 	} else if (isCell) {
 		double *R = a.scratch + g.off + c;
@@ -984,6 +988,67 @@ QK_DEV void waveFence()
 {
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 	__builtin_amdgcn_wave_barrier();
+}
+// FUSEX, the two faces of a row a wave cannot form from its own lanes (64 cells have 65 faces, and the edge state left of lane 0 belongs to a cell
+// outside the wave): formed XROWS rows at a time — the lanes of side 0 the left faces, of side 1 the right faces of the next XROWS rows — and parked
+// in the edge store with the primitives of the two cells beyond either end of the row, which the reconstruction of the end lanes reads
+// entries of a row: 0, 1 the cells x0 - 2, x0 - 1; 2, 3 the cells x0 + 64, x0 + 65; 4 the right face (x0 + 64); 5 the left face (x0).  A row's entries are
+// copied into six spare slots of the wave's row buffer one step ahead (stageEdgeRow), off the dependency chain of the step that reads them.
+template <int NV> using EdgeRow = double[6][NV + 1];
+// lanes 0..5 copy entry `lane` of a row of the batch into slots 0, 1, 66, 67 (halo cells), 68 (right face), 69 (left face) of the wave's row buffer
+template <int NV> QK_DEV void stageEdgeRow(double (*sx)[XW], const EdgeRow<NV> &row)
+{
+	const int t6 = static_cast<int>(threadIdx.x);
+	if (t6 < 6) {
+		const int slot = (t6 < 2) ? t6 : 64 + t6;
+#pragma unroll
+		for (int n = 0; n < NV + 1; ++n) {
+			sx[n][slot] = row[t6][n];
+		}
+	}
+}
+// the batch pass: the wave-edge faces (x0: the wave's first cell) and halo primitives of the rows row0 .. row0 + XROWS - 1 (clamped to hi) of plane ot
+template <int ORDER, int NS>
+QK_DEV void fusexEdgeBatch(SweepArgs const &a, Eos const &eos, RA4 const &Uin, SGeom const &g, const int64_t (&st)[3], const double *S, int x0, int row0, int hi, int ot, EdgeRow<NVAR + NS> *edge)
+{
+	constexpr int NV = NVAR + NS;
+	const int64_t T = a.total_cells;
+	const int tx = static_cast<int>(threadIdx.x);
+	const int side = (tx / XROWS) & 1; // (lanes beyond 2 * XROWS repeat the work of the first ones: same values to the same slots)
+	const int brow = tx & (XROWS - 1);
+	const int mrow = min(row0 + brow, hi);
+	const int f = x0 + 64 * side; // the face: between cells f - 1 and f
+	int64_t ub = Uin.idx(f - 3, mrow, ot);
+	double qb[6][NV], Uc[NVAR];
+#pragma unroll
+	for (int m = 0; m < 6; ++m, ++ub) {
+		loadPrims<NS>(Uin, ub, eos, a.reconstruct_eint, a.prim_in, qb[m], Uc);
+	}
+	const int64_t cb = (f - 1 - g.glo[0]) + (mrow - g.glo[1]) * st[1] + (ot - g.glo[2]) * st[2];
+	const double chiL = S[cb], chiR = S[cb + 1];
+	const double DyL = S[(S_AUX + 2) * T + cb], DyR = S[(S_AUX + 2) * T + cb + 1];
+	const double DzL = S[(S_AUX + 3) * T + cb], DzR = S[(S_AUX + 3) * T + cb + 1];
+	double qLb[NV], qRb[NV], Fb[NV], vfb;
+#pragma unroll
+	for (int n = 0; n < NV; ++n) { // (the two cells of the face variable by variable: the batch runs on top of the full register window of the march)
+		double unused;
+		reconstructVar<ORDER>(chiL, qb[0][n], qb[1][n], qb[2][n], qb[3][n], qb[4][n], unused, qLb[n]);
+		reconstructVar<ORDER>(chiR, qb[1][n], qb[2][n], qb[3][n], qb[4][n], qb[5][n], qRb[n], unused);
+	}
+	faceFluxAll<0, QK_RIEMANN_HLLC, false, NS>(eos, a.reconstruct_eint, 3, qLb, qRb, qb[3][PVX] - qb[2][PVX], DyL, DyR, DzL, DzR, a.K_visc, Fb, vfb);
+	double(*ed)[NV + 1] = edge[brow];
+	double *ef = ed[5 - side];
+#pragma unroll
+	for (int n = 0; n < NV; ++n) {
+		ef[n] = Fb[n];
+	}
+	ef[NV] = vfb;
+	// halo cells of the row: x0 - 2, x0 - 1 (left face: cells f - 2, f - 1) and x0 + 64, x0 + 65 (right face: cells f, f + 1)
+#pragma unroll
+	for (int n = 0; n < NV; ++n) {
+		ed[2 * side][n] = (side != 0) ? qb[3][n] : qb[1][n];
+		ed[2 * side + 1][n] = (side != 0) ? qb[4][n] : qb[2][n];
+	}
 }
 template <int DIR, int ORDER, int STAGE, bool LAST, int NS, bool CARRY, bool TWOD = false, bool FOFC = false, bool FUSEX = false>
 __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos eos)
@@ -1060,30 +1125,11 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 	}
 	constexpr bool RING = LAST && (STAGE == 1);
 	__shared__ double s_ring[RING ? 3 : 1][RING ? NV : 1][RING ? 64 * MARCH_BY : 1];
-	__shared__ double s_fx[FUSEX ? MARCH_BY : 1][FUSEX ? NV + 2 : 1][FUSEX ? XW : 1];
-	// FUSEX, the two faces of a row a wave cannot form from its own lanes (64 cells have 65 faces, and the edge state left of lane 0 belongs to a cell
-	// outside the wave): formed 32 rows at a time — lanes 0..31 the left faces, 32..63 the right faces of the next 32 rows — and parked here with
-	// the primitives of the two cells beyond either end of the row, which the reconstruction of the end lanes reads
-	// entries of a row: 0, 1 the cells x0 - 2, x0 - 1; 2, 3 the cells x0 + 64, x0 + 65; 4 the right face (x0 + 64); 5 the left face (x0).  A row's entries are
-	// copied into six spare slots of the wave's row buffer one step ahead (stageEdgeRow), off the dependency chain of the step that reads them.
-	__shared__ double s_edge[FUSEX ? MARCH_BY : 1][FUSEX ? XROWS : 1][6][FUSEX ? NV + 1 : 1];
+	__shared__ double s_fx[FUSEX ? MARCH_BY : 1][FUSEX ? NV + 2 : 1][FUSEX ? XW : 1]; // the wave's row buffer
+	__shared__ double s_edge[FUSEX ? MARCH_BY : 1][FUSEX ? XROWS : 1][6][FUSEX ? NV + 1 : 1]; // the wave's edge store (fusexEdgeBatch)
 	double chiPrev = 1.;
 	const int lself = (FUSEX && threadIdx.x == 0) ? 69 : static_cast<int>(threadIdx.x) + 2;
 	const int lnext = (FUSEX && threadIdx.x == 63) ? 68 : static_cast<int>(threadIdx.x) + 3;
-	// lanes 0..5 copy entry `lane` of row r of the batch into slots 0, 1, 66, 67 (halo cells), 68 (right face), 69 (left face) of the wave's row buffer
-	auto stageEdgeRow = [&](int r) {
-		if constexpr (FUSEX) {
-			const int t6 = static_cast<int>(threadIdx.x);
-			if (t6 < 6) {
-				const int slot = (t6 < 2) ? t6 : 64 + t6;
-				const double *src = s_edge[threadIdx.y][r][t6];
-#pragma unroll
-				for (int n = 0; n < NV + 1; ++n) {
-					s_fx[threadIdx.y][n][slot] = src[n];
-				}
-			}
-		}
-	};
 	const int tid = threadIdx.y * 64 + threadIdx.x;
 	const bool ring = RING && a.same_old;
 	int slot = 0;
@@ -1098,12 +1144,12 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 		}
 	}
 
-	// QK_MARCH_PREFETCH (A/B knob, default 1): the newest cell of the NEXT step is requested one step ahead (the fab holds the cell one beyond the last one a
-	// march converts: 4 ghost cells, 3 of them read), so that a wave does not park on the round trip of the cell it is about to convert.  Six more doubles in
-	// flight: not for the fused XY sweep, which sits at the 256-register limit of two waves per SIMD.  Same loads, same arithmetic: no bit changes.
+	// The newest cell of the NEXT step is requested one step ahead (the fab holds the cell one beyond the last one a march converts: 4 ghost cells, 3 of
+	// them read), so that a wave does not park on the round trip of the cell it is about to convert.  Six more doubles in flight: not for the fused XY
+	// sweep, which sits at the 256-register limit of two waves per SIMD.  Same loads, same arithmetic: no bit changes.
 	// Measured (profiles/round6/ab6_march_prefetch.txt): the Z sweep 0.873 -> 0.837 ms at 256^3, 6.61 -> 6.31 ms at 512^3 (234 -> 246 registers, no
 	// scratch); requesting the pre-pass results (chi, D_v, D_w) of the next cell as well gives the gain back (252 registers).
-	constexpr bool PFQ = (QK_MARCH_PREFETCH != 0) && !FUSEX && NS == 0; // (with passive scalars the six doubles push 21 instantiations past 256 registers: one wave per SIMD)
+	constexpr bool PFQ = !FUSEX && NS == 0; // (with passive scalars the six doubles push 21 instantiations past 256 registers: one wave per SIMD)
 	double Un[NVAR];
 	if constexpr (PFQ) {
 #pragma unroll
@@ -1128,23 +1174,9 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 					Uc[n] = Un[n];
 					Un[n] = Uin.p[u + ums + Uin.ns * n];
 				}
+				primsOf<NS>(Uin, u, eos, a.reconstruct_eint, a.prim_in, Uc, q[4]);
 			} else {
-#pragma unroll
-				for (int n = 0; n < NVAR; ++n) {
-					Uc[n] = Uin.p[u + Uin.ns * n];
-				}
-			}
-			if (a.prim_in) { // (uniform) the input array holds the primitives
-#pragma unroll
-				for (int n = 0; n < NVAR; ++n) {
-					q[4][n] = Uc[n];
-				}
-			} else {
-				consToPrim(eos, a.reconstruct_eint, Uc, q[4]);
-			}
-#pragma unroll
-			for (int n = NVAR; n < NV; ++n) { // passive scalars are reconstructed as they are stored
-				q[4][n] = Uin.p[u + Uin.ns * n];
+				loadPrims<NS>(Uin, u, eos, a.reconstruct_eint, a.prim_in, q[4], Uc);
 			}
 			if constexpr (RING) {
 				if (ring) {
@@ -1165,129 +1197,49 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 		const double chi = S[(S_AUX + 0) * T + cc];
 		const double dV = S[(S_AUX + 1 + AV) * T + cc];
 		const double dW = S[(S_AUX + 1 + AW) * T + cc];
-		// The accumulator of cell cc-1 (and in stage 2 the stage-1 flux of this step's face) are requested BEFORE the reconstruction and the
+		// this step's face, between cells cc-1 and cc (index = march coordinate of cc), and the cell cu = cc-1 it completes (from step 6 on)
+		int fidx[3], cidx[3];
+		fidx[0] = cidx[0] = i;
+		fidx[OT] = cidx[OT] = ot;
+		fidx[DIR] = lo + (step - 5);
+		cidx[DIR] = lo + (step - 6);
+		const int64_t cu = cc - ms;
+		// The accumulator of cell cu (and in stage 2 the stage-1 flux of this step's face) are requested BEFORE the reconstruction and the
 		// Riemann solve instead of where they are used: behind the face-flux stores they could not be hoisted by the compiler (may-alias),
 		// and a wave parked on them for a full memory round trip per step (SQ_WAIT_ANY 59 % of the wave cycles at 2 waves per SIMD).
 		double rhs_in[NV + 1], F1[NV + 1];
-		int fidx[3];
-		fidx[0] = i;
-		fidx[OT] = ot;
-		fidx[DIR] = lo + (step - 5);
 		if (step >= 6) {
-			const int64_t cu = cc - ms;
 			if constexpr (FUSEX) {
-				// the X sweep of the row this step completes (cell cu = cc - 1: primitives q[1], chi of the step before, D_z = dVprev)
+				// the X sweep of the row this step completes (cell cu: primitives q[1], chi of the step before, D_z = dVprev)
 				double(*sx)[XW] = s_fx[threadIdx.y];
-				const int tx = static_cast<int>(threadIdx.x);
-				const int l = tx + 2;
+				EdgeRow<NV> *edge = s_edge[threadIdx.y];
 				const int rr = (step - 6) & (XROWS - 1);
 				if (rr == 0) { // (uniform) the wave-edge faces and halo primitives of the next XROWS rows
-					const int side = (tx / XROWS) & 1; // (lanes beyond 2 * XROWS repeat the work of the first ones: same values to the same slots)
-					const int brow = tx & (XROWS - 1);
-					const int mrow = min(lo + (step - 6) + brow, hi);
-					const int f = bx.lo[0] + bix * 64 + 64 * side; // the face: between cells f - 1 and f
-					int64_t ub = Uin.idx(f - 3, mrow, ot);
-					double qb[6][NV];
-#pragma unroll
-					for (int m = 0; m < 6; ++m, ++ub) {
-						double Uc[NVAR];
-#pragma unroll
-						for (int n = 0; n < NVAR; ++n) {
-							Uc[n] = Uin.p[ub + Uin.ns * n];
-						}
-						if (a.prim_in) {
-#pragma unroll
-							for (int n = 0; n < NVAR; ++n) {
-								qb[m][n] = Uc[n];
-							}
-						} else {
-							consToPrim(eos, a.reconstruct_eint, Uc, qb[m]);
-						}
-#pragma unroll
-						for (int n = NVAR; n < NV; ++n) {
-							qb[m][n] = Uin.p[ub + Uin.ns * n];
-						}
-					}
-					const int64_t cb = (f - 1 - g.glo[0]) + (mrow - g.glo[1]) * st[1] + (ot - g.glo[2]) * st[2];
-					const double chiL = S[cb], chiR = S[cb + 1];
-					const double DyL = S[(S_AUX + 2) * T + cb], DyR = S[(S_AUX + 2) * T + cb + 1];
-					const double DzL = S[(S_AUX + 3) * T + cb], DzR = S[(S_AUX + 3) * T + cb + 1];
-					double qLb[NV], qRb[NV], Fb[NV], vfb;
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						double am_, ap_;
-						cellEdges<ORDER>(qb[0][n], qb[1][n], qb[2][n], qb[3][n], qb[4][n], am_, ap_);
-						flattenEdges(chiL, qb[2][n], am_, ap_);
-						qLb[n] = ap_;
-						cellEdges<ORDER>(qb[1][n], qb[2][n], qb[3][n], qb[4][n], qb[5][n], am_, ap_);
-						flattenEdges(chiR, qb[3][n], am_, ap_);
-						qRb[n] = am_;
-					}
-					{
-						Wave wv;
-						faceFlux<0, QK_RIEMANN_HLLC>(eos, a.reconstruct_eint, 3, qLb, qRb, qb[3][PVX] - qb[2][PVX], DyL, DyR, DzL, DzR, a.K_visc, Fb, vfb,
-									     NS > 0 ? &wv : nullptr);
-#pragma unroll
-						for (int n = NVAR; n < NV; ++n) {
-							Fb[n] = scalarFlux<QK_RIEMANN_HLLC>(wv, qLb[n], qRb[n]);
-						}
-					}
-					double(*ed)[NV + 1] = s_edge[threadIdx.y][brow];
-					double *ef = ed[5 - side];
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						ef[n] = Fb[n];
-					}
-					ef[NV] = vfb;
-					// halo cells of the row: x0 - 2, x0 - 1 (left face: cells f - 2, f - 1) and x0 + 64, x0 + 65 (right face: cells f, f + 1)
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						ed[2 * side][n] = (side != 0) ? qb[3][n] : qb[1][n];
-						ed[2 * side + 1][n] = (side != 0) ? qb[4][n] : qb[2][n];
-					}
+					fusexEdgeBatch<ORDER, NS>(a, eos, Uin, g, st, S, bx.lo[0] + bix * 64, cidx[DIR], hi, ot, edge);
 					waveFence();
-					stageEdgeRow(0);
+					stageEdgeRow<NV>(sx, edge[0]);
 				}
+				// The X sweep of the row inside the wave: primitives, then right-edge states + D_y, D_z, then fluxes travel through the row buffer.
+				// (These 25 lines stay in the loop body: behind ANY function boundary — a QK_DEV function or a lambda, whatever its parameters — the
+				// same text costs the fused kernel 14 spilled registers and the second wave per SIMD: 254 VGPRs + 14 AGPRs, occupancy 1.)
 				const double Dy = S[(S_AUX + 2) * T + cu];
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					sx[n][l] = q[1][n];
-				}
+				const int l = static_cast<int>(threadIdx.x) + 2;
+				putColumn(sx, l, q[1]);
 				waveFence();
 				double amx[NV], apx[NV];
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					cellEdges<ORDER>(sx[n][l - 2], sx[n][l - 1], q[1][n], sx[n][l + 1], sx[n][l + 2], amx[n], apx[n]);
-					flattenEdges(chiPrev, q[1][n], amx[n], apx[n]);
-				}
+				reconstructCell<ORDER>(chiPrev, q[1], [&](int m, int n) { return sx[n][l + m]; }, amx, apx);
 				const double uLeft = sx[PVX][l - 1];
 				waveFence();
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					sx[n][l] = apx[n];
-				}
+				putColumn(sx, l, apx);
 				sx[NV][l] = Dy;
 				sx[NV + 1][l] = dVprev;
 				waveFence();
 				double qLx[NV], Fx[NV], vfx;
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					qLx[n] = sx[n][l - 1];
-				}
+				getColumn(sx, l - 1, qLx);
 				const double dvl = sx[NV][l - 1], dwl = sx[NV + 1][l - 1];
-				{
-					Wave wv;
-					faceFlux<0, QK_RIEMANN_HLLC>(eos, a.reconstruct_eint, 3, qLx, amx, q[1][PVX] - uLeft, dvl, Dy, dwl, dVprev, a.K_visc, Fx, vfx, NS > 0 ? &wv : nullptr);
-#pragma unroll
-					for (int n = NVAR; n < NV; ++n) {
-						Fx[n] = scalarFlux<QK_RIEMANN_HLLC>(wv, qLx[n], amx[n]);
-					}
-				}
+				faceFluxAll<0, QK_RIEMANN_HLLC, false, NS>(eos, a.reconstruct_eint, 3, qLx, amx, q[1][PVX] - uLeft, dvl, Dy, dwl, dVprev, a.K_visc, Fx, vfx);
 				waveFence();
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					sx[n][l] = Fx[n];
-				}
+				putColumn(sx, l, Fx);
 				sx[NV][l] = vfx;
 				waveFence();
 				// every lane reads the fluxes of its two faces back: its own slot and its right neighbour's — but lane 0 its left face from slot 69 and
@@ -1299,20 +1251,16 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				rhs_in[NV] = (sx[NV][lnext] - sx[NV][lself]) / a.dx0; // :803
 				waveFence();
 				if (rr + 1 < XROWS) {
-					stageEdgeRow(rr + 1);
+					stageEdgeRow<NV>(sx, edge[rr + 1]);
 				}
 			} else {
 #pragma unroll
-			for (int n = 0; n < NV + 1; ++n) {
-				rhs_in[n] = streamLoad(&S[(S_RHS + n) * T + cu]);
-			}
+				for (int n = 0; n < NV + 1; ++n) {
+					rhs_in[n] = streamLoad(&S[(S_RHS + n) * T + cu]);
+				}
 			}
 			if (LAST && !ring && !(CARRY && STAGE == 2)) { // the old state of the cell this step completes (stage 2 of the carried form: S replaces it)
-				int uc[3];
-				uc[0] = i;
-				uc[OT] = ot;
-				uc[DIR] = lo + (step - 6);
-				const int64_t co = Uold.idx(uc[0], uc[1], uc[2]);
+				const int64_t co = Uold.idx(cidx[0], cidx[1], cidx[2]);
 #pragma unroll
 				for (int n = 0; n < NV; ++n) {
 					Uo[n] = Uold.p[co + Uold.ns * n];
@@ -1320,11 +1268,7 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 			}
 			if (CARRY && LAST && STAGE == 2) { // the half step and the pressure stage 1 stored for this cell (F1[] is free in this mode)
 				RA4 R1(a.rhs1[b]);
-				int uc[3];
-				uc[0] = i;
-				uc[OT] = ot;
-				uc[DIR] = lo + (step - 6);
-				const int64_t c1 = R1.idx(uc[0], uc[1], uc[2]);
+				const int64_t c1 = R1.idx(cidx[0], cidx[1], cidx[2]);
 #pragma unroll
 				for (int n = 0; n < NV + 1; ++n) {
 					F1[n] = R1.p[c1 + R1.ns * n];
@@ -1332,106 +1276,24 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 			}
 		}
 		if (!CARRY && STAGE == 2 && step >= 5) {
-			RA4 HF(a.halfFlux[b]);
-			RA4 HV(a.halfVel[b]);
-			const int64_t o = HF.idx(fidx[0], fidx[1], fidx[2]);
-#pragma unroll
-			for (int n = 0; n < NV; ++n) {
-				F1[n] = HF.p[o + HF.ns * n];
-			}
-			F1[NV] = HV(fidx[0], fidx[1], fidx[2]);
+			loadF1<NV>(a, b, fidx, F1);
 		}
 		double am[NV], ap[NV];
-#pragma unroll
-		for (int n = 0; n < NV; ++n) {
-			cellEdges<ORDER>(q[0][n], q[1][n], q[2][n], q[3][n], q[4][n], am[n], ap[n]);
-			flattenEdges(chi, q[2][n], am[n], ap[n]);
-		}
+		reconstructCell<ORDER>(chi, q[2], [&](int m, int n) { return q[2 + m][n]; }, am, ap);
 		if (step >= 5) {
-			// face between cells cc-1 and cc, index = (march coordinate of cc)
 			const double du = q[2][PVX + DIR] - q[1][PVX + DIR];
 			double F[NV], vf;
-			{
-				Wave wv;
-				faceFlux<DIR, QK_RIEMANN_HLLC, TWOD>(eos, a.reconstruct_eint, TWOD ? 2 : 3, apPrev, am, du, dVprev, dV, dWprev, dW, a.K_visc, F, vf,
-								     NS > 0 ? &wv : nullptr);
-#pragma unroll
-				for (int n = NVAR; n < NV; ++n) {
-					F[n] = scalarFlux<QK_RIEMANN_HLLC>(wv, apPrev[n], am[n]);
-				}
+			faceFluxAll<DIR, QK_RIEMANN_HLLC, TWOD, NS>(eos, a.reconstruct_eint, TWOD ? 2 : 3, apPrev, am, du, dVprev, dV, dWprev, dW, a.K_visc, F, vf);
+			bool marked = false;
+			if (maskCol && fidx[DIR] >= maskLo && cidx[DIR] <= maskHi) { // the face's cells fidx - 1 and fidx along the march
+				CA4 M(a.fluxMask[b]);
+				const int m0 = (cidx[DIR] >= maskLo) ? M(cidx[0], cidx[1], cidx[2]) : 0;
+				const int m1 = (fidx[DIR] <= maskHi) ? M(fidx[0], fidx[1], fidx[2]) : 0;
+				marked = (m0 | m1) != 0;
 			}
-			// FOFC pass: a face that touches a cell the first pass flagged takes the first-order flux of the old state (see firstOrderFlux)
-			bool firstOrder = false;
-			if constexpr (FOFC) {
-				CIA4 flag(a.redoFlag[b]);
-				int fm[3] = {fidx[0], fidx[1], fidx[2]};
-				fm[DIR] -= 1;
-				firstOrder = (flag(fm[0], fm[1], fm[2]) != 0) || (flag(fidx[0], fidx[1], fidx[2]) != 0);
-			}
-			auto replaceByFirstOrder = [&]() {
-				double qLo[NV], qRo[NV];
-				if (STAGE == 1) { // the old state is the input state: the window holds its primitives (cells cc - 1 and cc)
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						qLo[n] = q[1][n];
-						qRo[n] = q[2][n];
-					}
-				} else {
-					int fm[3] = {fidx[0], fidx[1], fidx[2]};
-					fm[DIR] -= 1;
-					primOfCell<NS>(Uold, eos, a.reconstruct_eint, fm[0], fm[1], fm[2], qLo);
-					primOfCell<NS>(Uold, eos, a.reconstruct_eint, fidx[0], fidx[1], fidx[2], qRo);
-				}
-				firstOrderFlux<DIR, NS, TWOD, TWOD ? 2 : 3>(eos, a.reconstruct_eint, qLo, qRo, F, vf);
-			};
-			if (CARRY) {
-				// carried right-hand side: no face arrays — except on the marked faces of a level with refined children
-				if (maskCol && fidx[DIR] >= maskLo && fidx[DIR] - 1 <= maskHi) { // the face's cells fidx - 1 and fidx along the march
-					CA4 M(a.fluxMask[b]);
-					int fm[3] = {fidx[0], fidx[1], fidx[2]};
-					fm[DIR] -= 1;
-					const int m0 = (fm[DIR] >= maskLo) ? M(fm[0], fm[1], fm[2]) : 0;
-					const int m1 = (fidx[DIR] <= maskHi) ? M(fidx[0], fidx[1], fidx[2]) : 0;
-					if ((m0 | m1) != 0) {
-						maskedFaceFlux<STAGE, NV>(a, b, fidx[0], fidx[1], fidx[2], F);
-					}
-				}
-			} else if (STAGE == 1 && FOFC) {
-				if (firstOrder) { // (halfFlux keeps the uncorrected stage-1 flux of the first pass)
-					replaceByFirstOrder();
-				}
-			} else if (STAGE == 1) {
-				if (live) {
-					WA4 HF(a.halfFlux[b]);
-					WA4 HV(a.halfVel[b]);
-					const int64_t o = HF.idx(fidx[0], fidx[1], fidx[2]);
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						HF.p[o + HF.ns * n] = F[n];
-					}
-					HV(fidx[0], fidx[1], fidx[2]) = vf;
-				}
-			} else {
-#pragma unroll
-				for (int n = 0; n < NV; ++n) {
-					F[n] = 0.5 * F1[n] + 0.5 * F[n];
-				}
-				vf = 0.5 * F1[NV] + 0.5 * vf;
-				if (FOFC && firstOrder) {
-					replaceByFirstOrder(); // flux_rk2 of this face as a whole
-				}
-				if (a.store_rk2 && live) {
-					WA4 RF(a.rk2Flux[b]);
-					const int64_t o2 = RF.idx(fidx[0], fidx[1], fidx[2]);
-#pragma unroll
-					for (int n = 0; n < NV; ++n) {
-						RF.p[o2 + RF.ns * n] = F[n];
-					}
-				}
-			}
+			settleFace<STAGE, CARRY, FOFC, DIR, NS, TWOD>(a, eos, TWOD ? 2 : 3, b, fidx, live, marked, F1, q[1], q[2], F, vf); // (stage 1: the window holds the old state)
 			if (step >= 6) {
-				// update cell u = cc - 1 (march coordinate lo + step - 6)
-				const int64_t cu = cc - ms;
+				// update cell cu (march coordinate lo + step - 6)
 				double rhs[NV];
 #pragma unroll
 				for (int n = 0; n < NV; ++n) {
@@ -1439,12 +1301,8 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				}
 				const double div_v = rhs_in[NV] + (vf - vfPrev) / a.dx;
 				if (LAST) {
-					int u[3];
-					u[0] = i;
-					u[OT] = ot;
-					u[DIR] = lo + (step - 6);
 					if (live) {
-						updateCellFrom<NS, CARRY ? STAGE : 0, FOFC, TWOD ? 2 : 3>(a, eos, ec, b, u[0], u[1], u[2], Uo, rhs, div_v, F1, sig0, sig1,
+						updateCellFrom<NS, CARRY ? STAGE : 0, FOFC, TWOD ? 2 : 3>(a, eos, ec, b, cidx[0], cidx[1], cidx[2], Uo, rhs, div_v, F1, sig0, sig1,
 													    (STAGE == 1) && a.same_old && !a.reconstruct_eint && !a.prim_in, q[1][PPRES]);
 					}
 				} else if (live) {
@@ -1470,15 +1328,7 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 		chiPrev = chi;
 	}
 	if (LAST && a.max_signal != nullptr) {
-		// wave reduction (64 lanes), one atomic per wave; max is exact, so the result is deterministic
-		for (int off = 32; off > 0; off >>= 1) {
-			sig0 = smax(sig0, __shfl_xor(sig0, off));
-			sig1 = smax(sig1, __shfl_xor(sig1, off));
-		}
-		if (threadIdx.x == 0) {
-			atomicMaxNonNeg(&a.max_signal[0], sig0);
-			atomicMaxNonNeg(&a.max_signal[1], sig1);
-		}
+		reduceSignal(a.max_signal, sig0, sig1);
 	}
 }
 
@@ -1567,26 +1417,74 @@ auto buildGeom(qk_level *lev) -> int
 	return QK_OK;
 }
 
-template <int ORDER, int STAGE, int NS, bool CARRY, bool FOFC = false> void launchSweeps(qk_level *lev, hipStream_t s, SweepArgs a, Eos eos, const qk_hydro_stage_args *args)
+// Segments of the pre-pass along z.  Every segment pays 6 planes of warm-up (own columns only), a CU holds two workgroups (512 slots on the chip), and
+// short segments keep the workgroups of neighbouring tiles at the same z, where their halo rows are still in the XCD's L2.  Measured
+// (profiles/round4/ab7_prepass_segments.txt): 256^3 in 128^3 boxes (304 tiles) 3 / 4 / 5 / 6 segments 0.419 / 0.428 / 0.405 / 0.423 ms —
+// the order of (idle share of the last round of workgroups) x (warm-up share); 512^3 (2432 tiles) 1 / 2 / 3 / 4 / 5 / 6 segments 3.10 /
+// 3.00 / 2.96 / 2.88 / 2.99 / 3.02 ms.  So: segments of about 30 planes; with few rounds of workgroups the neighbour count that wastes
+// least.  (A small level: shorter segments, see marchSegments.)
+auto prePassSegments(const qk_level *lev, int xt, int yt) -> int
 {
-	// the X sweep inside the Y sweep (FUSEX): 3-D, carried form without a flux mask, every box a whole number of 64-cell waves wide
-	bool fusex = false;
-	if constexpr (CARRY && !FOFC && NS == 0) { // (with passive scalars the fused kernel needs more than 256 registers: one wave per SIMD)
-		const char *e = std::getenv("QK_FUSEX"); // (read per launch: tests and A/B runs switch it inside one process)
-		const int want = (e != nullptr) ? std::atoi(e) : 1;
-		fusex = want != 0 && lev->ndim == 3 && a.fluxMask == nullptr;
-		for (int b = 0; fusex && b < lev->nboxes; ++b) {
-			fusex = (lev->boxes[b].hi[0] - lev->boxes[b].lo[0] + 1) % 64 == 0;
+	if (const char *e = std::getenv("QK_PRE_SEGMENTS")) {
+		return std::max(1, std::atoi(e));
+	}
+	const bool small = static_cast<int64_t>(lev->nboxes) * lev->maxlen[0] * lev->maxlen[1] * lev->maxlen[2] < smallLevelCells();
+	const int64_t tiles = static_cast<int64_t>(xt) * yt * lev->nboxes;
+	const int nplanes = lev->maxlen[2] + 2;
+	if (small) {
+		return static_cast<int>(std::min<int64_t>((1024 + tiles - 1) / tiles, std::max(1, nplanes / smallMinLen())));
+	}
+	const int base = std::max(1, std::min(8, (nplanes + 15) / 30));
+	int nseg = base;
+	const double slots = 512.0;
+	if (static_cast<double>(tiles) * base / slots < 6.0) {
+		double best = 1e300;
+		for (int c = std::max(1, base - 1); c <= base + 1; ++c) {
+			const double rounds = static_cast<double>(tiles) * c / slots;
+			const int seglen = (nplanes + c - 1) / c;
+			const double cost = (std::ceil(rounds) / rounds) * (static_cast<double>(seglen + 6) / seglen);
+			if (cost < best) {
+				best = cost;
+				nseg = c;
+			}
 		}
 	}
+	return nseg;
+}
+
+// the arguments of the sweep along direction d: its face arrays and spacing
+auto sweepArgsFor(SweepArgs a, const qk_hydro_stage_args *args, int d) -> SweepArgs
+{
+	a.halfFlux = args->halfFlux[d];
+	a.halfVel = args->halfVel[d];
+	a.rk2Flux = args->fluxRk2[d];
+	a.inv_dx = 1.0 / args->dx[d];
+	a.dx = args->dx[d];
+	return a;
+}
+
+// Does the X sweep ride inside the Y march (FUSEX) on this level?  A 3-D level in the carried form without a flux mask and without passive scalars
+// (with them the fused kernel needs more than 256 registers: one wave per SIMD), every box a whole number of 64-cell waves wide.
+auto fusexApplies(const qk_level *lev, SweepArgs const &a, bool carry, int nscalars) -> bool
+{
+	const char *e = std::getenv("QK_FUSEX"); // (read per launch: tests and A/B runs switch it inside one process)
+	if (!carry || nscalars != 0 || lev->ndim != 3 || a.fluxMask != nullptr || (e != nullptr && std::atoi(e) == 0)) {
+		return false;
+	}
+	for (int b = 0; b < lev->nboxes; ++b) {
+		if ((lev->boxes[b].hi[0] - lev->boxes[b].lo[0] + 1) % 64 != 0) {
+			return false;
+		}
+	}
+	return true;
+}
+
+template <int ORDER, int STAGE, int NS, bool CARRY, bool FOFC = false> void launchSweeps(qk_level *lev, hipStream_t s, SweepArgs a, Eos eos, const qk_hydro_stage_args *args)
+{
+	const bool fusex = fusexApplies(lev, a, CARRY, NS);
 	// X
 	if (!fusex) {
-		SweepArgs ax = a;
-		ax.halfFlux = args->halfFlux[0];
-		ax.halfVel = args->halfVel[0];
-		ax.rk2Flux = args->fluxRk2[0];
-		ax.inv_dx = 1.0 / args->dx[0];
-		ax.dx = args->dx[0];
+		const SweepArgs ax = sweepArgsFor(a, args, 0);
 		const int64_t slab = static_cast<int64_t>(lev->maxlen[0] + 2 * NG) * lev->maxlen[1];
 		const dim3 grid(static_cast<unsigned>((slab + XOUT - 1) / XOUT), static_cast<unsigned>(lev->maxlen[2]), static_cast<unsigned>(lev->nboxes));
 		ProfScope ps(lev->ctx, s, "k_sweep_x");
@@ -1603,58 +1501,67 @@ template <int ORDER, int STAGE, int NS, bool CARRY, bool FOFC = false> void laun
 	if (lev->ndim == 1) {
 		return;
 	}
-	if (lev->ndim == 2) { // Y of a 2-D build (index-swap view) + epilogue
-		if constexpr (!CARRY) {
-			SweepArgs ay = a;
-			ay.same_old = (args->U_in == args->U_old);
-			ay.halfFlux = args->halfFlux[1];
-			ay.halfVel = args->halfVel[1];
-			ay.rk2Flux = args->fluxRk2[1];
-			ay.inv_dx = 1.0 / args->dx[1];
-			ay.dx = args->dx[1];
-			ay.nseg = marchSegments(lev, 1, 2);
-			const dim3 grid((lev->maxlen[0] + 63) / 64, (lev->maxlen[2] + MARCH_BY - 1) / MARCH_BY, lev->nboxes * ay.nseg);
-			ProfScope ps(lev->ctx, s, "k_sweep_y");
-			hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, true, NS, false, true, FOFC>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
-		}
-		return;
-	}
-	// Y
+	// Y: the final sweep of a 2-D build (index-swap view, + epilogue)
 	{
-		SweepArgs ay = a;
-		ay.halfFlux = args->halfFlux[1];
-		ay.halfVel = args->halfVel[1];
-		ay.rk2Flux = args->fluxRk2[1];
-		ay.inv_dx = 1.0 / args->dx[1];
-		ay.dx = args->dx[1];
+		SweepArgs ay = sweepArgsFor(a, args, 1);
+		ay.same_old = (lev->ndim == 2) && (args->U_in == args->U_old);
 		ay.nseg = marchSegments(lev, 1, 2);
 		ay.inv_dx0 = 1.0 / args->dx[0];
 		ay.dx0 = args->dx[0];
 		const dim3 grid((lev->maxlen[0] + 63) / 64, (lev->maxlen[2] + MARCH_BY - 1) / MARCH_BY, lev->nboxes * ay.nseg);
+		ProfScope ps(lev->ctx, s, fusex ? "k_sweep_xy" : "k_sweep_y");
+		if (lev->ndim == 2) {
+			if constexpr (!CARRY) {
+				hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, true, NS, false, true, FOFC>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
+			}
+			return;
+		}
 		if constexpr (CARRY && !FOFC && NS == 0) {
 			if (fusex) {
-				ProfScope ps(lev->ctx, s, "k_sweep_xy");
 				hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, false, NS, CARRY, false, FOFC, true>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
 			}
 		}
 		if (!fusex) {
-			ProfScope ps(lev->ctx, s, "k_sweep_y");
 			hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, false, NS, CARRY, false, FOFC>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
 		}
 	}
 	// Z (+ epilogue)
 	{
-		SweepArgs az = a;
+		SweepArgs az = sweepArgsFor(a, args, 2);
 		az.same_old = (args->U_in == args->U_old);
-		az.halfFlux = args->halfFlux[2];
-		az.halfVel = args->halfVel[2];
-		az.rk2Flux = args->fluxRk2[2];
-		az.inv_dx = 1.0 / args->dx[2];
-		az.dx = args->dx[2];
 		az.nseg = marchSegments(lev, 2, 1);
 		const dim3 grid((lev->maxlen[0] + 63) / 64, (lev->maxlen[1] + MARCH_BY - 1) / MARCH_BY, lev->nboxes * az.nseg);
 		ProfScope ps(lev->ctx, s, "k_sweep_z");
 		hipLaunchKernelGGL((k_sweep_march<2, ORDER, STAGE, true, NS, CARRY, false, FOFC>), grid, dim3(64, MARCH_BY), 0, s, az, eos);
+	}
+}
+
+// the runtime tuple (order 1..3, passive scalars 0..3, stage 1 | 2, form exact | carried | first-order correction pass) -> its instantiation
+template <int ORDER, int NS> void launchStage(qk_level *lev, hipStream_t s, SweepArgs const &a, Eos const &eos, const qk_hydro_stage_args *args)
+{
+	auto form = [&](auto stage) {
+		constexpr int STAGE = decltype(stage)::value;
+		if (args->fofc_pass != 0) {
+			launchSweeps<ORDER, STAGE, NS, false, true>(lev, s, a, eos, args);
+		} else if (args->rk2_carry_rhs != 0) {
+			launchSweeps<ORDER, STAGE, NS, true>(lev, s, a, eos, args);
+		} else {
+			launchSweeps<ORDER, STAGE, NS, false>(lev, s, a, eos, args);
+		}
+	};
+	if (args->stage == 1) {
+		form(std::integral_constant<int, 1>{});
+	} else {
+		form(std::integral_constant<int, 2>{});
+	}
+}
+template <int ORDER> void launchOrder(int nscalars, qk_level *lev, hipStream_t s, SweepArgs const &a, Eos const &eos, const qk_hydro_stage_args *args)
+{
+	switch (nscalars) {
+	case 0: return launchStage<ORDER, 0>(lev, s, a, eos, args);
+	case 1: return launchStage<ORDER, 1>(lev, s, a, eos, args);
+	case 2: return launchStage<ORDER, 2>(lev, s, a, eos, args);
+	default: return launchStage<ORDER, 3>(lev, s, a, eos, args);
 	}
 }
 
@@ -1745,38 +1652,7 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 	{
 		ProfScope ps(ctx, s, "k_pre");
 		const int xt = (lev->maxlen[0] + 2 + PT_X - 1) / PT_X, yt = (lev->maxlen[1] + 2 + PT_Y - 1) / PT_Y;
-		// Segments along z.  Every segment pays 6 planes of warm-up (own columns only), a CU holds two workgroups (512 slots on the chip), and
-		// short segments keep the workgroups of neighbouring tiles at the same z, where their halo rows are still in the XCD's L2.  Measured
-		// (profiles/round4/ab7_prepass_segments.txt): 256^3 in 128^3 boxes (304 tiles) 3 / 4 / 5 / 6 segments 0.419 / 0.428 / 0.405 / 0.423 ms —
-		// the order of (idle share of the last round of workgroups) x (warm-up share); 512^3 (2432 tiles) 1 / 2 / 3 / 4 / 5 / 6 segments 3.10 /
-		// 3.00 / 2.96 / 2.88 / 2.99 / 3.02 ms.  So: segments of about 30 planes; with few rounds of workgroups the neighbour count that wastes
-		// least.  (A small level: shorter segments, see marchSegments.)
-		const bool small = static_cast<int64_t>(lev->nboxes) * lev->maxlen[0] * lev->maxlen[1] * lev->maxlen[2] < smallLevelCells();
-		const int64_t tiles = static_cast<int64_t>(xt) * yt * lev->nboxes;
-		const int nplanes = lev->maxlen[2] + 2;
-		int nseg;
-		if (small) {
-			nseg = static_cast<int>(std::min<int64_t>((1024 + tiles - 1) / tiles, std::max(1, nplanes / smallMinLen())));
-		} else {
-			const int base = std::max(1, std::min(8, (nplanes + 15) / 30));
-			nseg = base;
-			const double slots = 512.0;
-			if (static_cast<double>(tiles) * base / slots < 6.0) {
-				double best = 1e300;
-				for (int c = std::max(1, base - 1); c <= base + 1; ++c) {
-					const double rounds = static_cast<double>(tiles) * c / slots;
-					const int seglen = (nplanes + c - 1) / c;
-					const double cost = (std::ceil(rounds) / rounds) * (static_cast<double>(seglen + 6) / seglen);
-					if (cost < best) {
-						best = cost;
-						nseg = c;
-					}
-				}
-			}
-		}
-		if (const char *e = std::getenv("QK_PRE_SEGMENTS")) {
-			nseg = std::max(1, std::atoi(e));
-		}
+		const int nseg = prePassSegments(lev, xt, yt);
 		const dim3 grid(static_cast<unsigned>(xt) * yt * lev->nboxes * nseg);
 		if (args->prim_in != 0) {
 			hipLaunchKernelGGL(k_pre3<true>, grid, dim3(PT_THREADS), 0, s, boxes, geom, args->U_in, scratch, T, eos, re, nseg, xt, yt, t->ndim);
@@ -1813,44 +1689,13 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 		a.dx3[d] = args->dx[d];
 	}
 
-#define QK_LAUNCH_NS(ORDER, NS)                                                                                                                      \
-	if (args->fofc_pass != 0) {                                                                                                                  \
-		if (args->stage == 1) {                                                                                                              \
-			launchSweeps<ORDER, 1, NS, false, true>(lev, s, a, eos, args);                                                               \
-		} else {                                                                                                                             \
-			launchSweeps<ORDER, 2, NS, false, true>(lev, s, a, eos, args);                                                               \
-		}                                                                                                                                    \
-	} else if (args->rk2_carry_rhs != 0) {                                                                                                              \
-		if (args->stage == 1) {                                                                                                              \
-			launchSweeps<ORDER, 1, NS, true>(lev, s, a, eos, args);                                                                      \
-		} else {                                                                                                                             \
-			launchSweeps<ORDER, 2, NS, true>(lev, s, a, eos, args);                                                                      \
-		}                                                                                                                                    \
-	} else if (args->stage == 1) {                                                                                                               \
-		launchSweeps<ORDER, 1, NS, false>(lev, s, a, eos, args);                                                                             \
-	} else {                                                                                                                                     \
-		launchSweeps<ORDER, 2, NS, false>(lev, s, a, eos, args);                                                                             \
-	}
-#define QK_LAUNCH(ORDER)                                                                                                                             \
-	switch (t->nscalars) {                                                                                                                       \
-	case 0:                                                                                                                                      \
-		QK_LAUNCH_NS(ORDER, 0) break;                                                                                                        \
-	case 1:                                                                                                                                      \
-		QK_LAUNCH_NS(ORDER, 1) break;                                                                                                        \
-	case 2:                                                                                                                                      \
-		QK_LAUNCH_NS(ORDER, 2) break;                                                                                                        \
-	default:                                                                                                                                     \
-		QK_LAUNCH_NS(ORDER, 3) break;                                                                                                        \
-	}
 	if (args->reconstruction_order == 3) {
-		QK_LAUNCH(3)
+		launchOrder<3>(t->nscalars, lev, s, a, eos, args);
 	} else if (args->reconstruction_order == 2) {
-		QK_LAUNCH(2)
+		launchOrder<2>(t->nscalars, lev, s, a, eos, args);
 	} else {
-		QK_LAUNCH(1)
+		launchOrder<1>(t->nscalars, lev, s, a, eos, args);
 	}
-#undef QK_LAUNCH_NS
-#undef QK_LAUNCH
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
