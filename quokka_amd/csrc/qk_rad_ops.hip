@@ -25,15 +25,118 @@ inline auto checkRad(qk_ctx *ctx, const qk_rad_traits *rt) -> int
 	}
 	if (rt->eddington_model < 0 || rt->eddington_model > 1) {
 		return setError(ctx, QK_ERR_UNSUPPORTED,
-				"opacity_model must be 0 (constant kappa), 1 (constant rho * kappa) or 2 (temperature power law), eddington_model 0 (Levermore) or 1 (1/3)");
+				"eddington_model must be 0 (Levermore closure) or 1 (Eddington approximation: 1/3)");
 	}
 	if (rt->beta_order < 0 || rt->beta_order > 3) {
 		return setError(ctx, QK_ERR_INVALID, "beta_order must be 0..3");
 	}
 	if (rt->ngroups < 0 || rt->ngroups > QK_MAX_GROUPS) {
-		return setError(ctx, QK_ERR_UNSUPPORTED, "ngroups must be 1 .. QK_MAX_GROUPS (8)");
+		return setError(ctx, QK_ERR_UNSUPPORTED, "ngroups must be 0 (read as 1) .. QK_MAX_GROUPS (8)");
 	}
 	return QK_OK;
+}
+
+// A run-time reconstruction order or build dimension as a compile-time constant: f(std::integral_constant<int, n>) for n = 3, 2 and 1.  The callers
+// have checked the range (QK_REQUIRE, lev->ndim); any other value takes <1>, as the ladders this replaces did.
+template <class F> void dispatchConst1to3(int n, F f)
+{
+	if (n == 3) {
+		f(std::integral_constant<int, 3>{});
+	} else if (n == 2) {
+		f(std::integral_constant<int, 2>{});
+	} else {
+		f(std::integral_constant<int, 1>{});
+	}
+}
+
+// the NRAD components from comp0 on of the cell or face at offset o = X.idx(i, j, k)
+template <class A> QK_DEV void loadRad(A const &X, int64_t o, int comp0, double out[NRAD])
+{
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		out[n] = X.p[o + X.ns * (comp0 + n)];
+	}
+}
+template <class A> QK_DEV void storeRad(A const &X, int64_t o, int comp0, const double in[NRAD])
+{
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		X.p[o + X.ns * (comp0 + n)] = in[n];
+	}
+}
+// The same with non-temporal hints, for the fused transport stage where they pay (measured on one box): on the flux-divergence accumulator the
+// X sweep's stores and the Z sweep's loads (Z -3.5 %, X -1.5 %), and the Z sweep's stores of the new radiation state and its loads of the substep's
+// starting state (Z another -2 %).  The Y sweep, which reads AND rewrites the accumulator, is 5 % slower with them and keeps plain accesses.
+template <class A> QK_DEV void loadRadNT(A const &X, int64_t o, int comp0, double out[NRAD])
+{
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		out[n] = __builtin_nontemporal_load(&X.p[o + X.ns * (comp0 + n)]);
+	}
+}
+template <class A> QK_DEV void storeRadNT(A const &X, int64_t o, int comp0, const double in[NRAD])
+{
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		__builtin_nontemporal_store(in[n], &X.p[o + X.ns * (comp0 + n)]);
+	}
+}
+
+// cons -> prim of one cell (radiation_system.hpp:603-610)
+QK_DEV void radPrim(Rad const &r, const double c[NRAD], double p[NRAD])
+{
+	p[0] = c[0];
+	const Recip RcE = recipOf(r.c * c[0]); // three quotients, one refined reciprocal (qk_device.hpp: same bits as three `/`)
+	p[1] = divBy(c[1], RcE);
+	p[2] = divBy(c[2], RcE);
+	p[3] = divBy(c[3], RcE);
+}
+
+// Face states by reconstruction ORDER: 3 PPM (ppmEdges), 2 PLM (hyperbolic_system.hpp:243-246 with the MC limiter, QuokkaSimulation.hpp:1948),
+// 1 donor cell.  A window p[6] holds the primitives of the cells face-3 .. face+2; cells RAD_M0 .. RAD_M1 of it are read.
+template <int ORDER> constexpr int RAD_M0 = (ORDER == 3) ? 0 : (ORDER == 2) ? 1 : 2;
+template <int ORDER> constexpr int RAD_M1 = (ORDER == 3) ? 5 : (ORDER == 2) ? 4 : 3;
+
+// component n of what cell face-1 gives to the face — PPM: its right edge; PLM: its limited slope
+template <int ORDER> QK_DEV auto radSeedCarry(const double p[6][NRAD], int n) -> double
+{
+	if constexpr (ORDER == 3) {
+		double am, ap;
+		ppmEdges(p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap);
+		return ap;
+	} else if constexpr (ORDER == 2) {
+		return MC(p[3][n] - p[2][n], p[2][n] - p[1][n]);
+	} else {
+		return 0.0; // (not read)
+	}
+}
+// component n of both states of the face, from the carry and from cell `face`; what that cell gives to the next face becomes the carry
+template <int ORDER> QK_DEV void radStepFace(const double p[6][NRAD], int n, double &carry, double &pL, double &pR)
+{
+	if constexpr (ORDER == 3) {
+		double am, ap;
+		ppmEdges(p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap);
+		pL = carry;
+		pR = am;
+		carry = ap;
+	} else if constexpr (ORDER == 2) {
+		const double rslope = MC(p[4][n] - p[3][n], p[3][n] - p[2][n]);
+		pL = p[2][n] + 0.25 * carry;
+		pR = p[3][n] - 0.25 * rslope;
+		carry = rslope;
+	} else {
+		pL = p[2][n];
+		pR = p[3][n];
+	}
+}
+// a face on its own: the first step of a march
+template <int ORDER> QK_DEV void radFaceStates(const double p[6][NRAD], double pL[NRAD], double pR[NRAD])
+{
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		double carry = radSeedCarry<ORDER>(p, n);
+		radStepFace<ORDER>(p, n, carry, pL[n], pR[n]);
+	}
 }
 
 template <int DIR>
@@ -48,32 +151,15 @@ void launchRadComputeFluxes(qk_level *lev, qk_stream s, Rad rad, qk_array4 *flux
 		RA4 R(right_t[b]);
 		RA4 U(cons_t[b]);
 		WA4 F(flux_t[b]);
-		const int im = i - unit(DIR, 0), jm = j - unit(DIR, 1), km = k - unit(DIR, 2);
 		const int pg = NRAD * static_cast<int>(blockIdx.z); // component offset of this block's photon group
 		double pL[NRAD], pR[NRAD], cL[NRAD], cR[NRAD], Fo[NRAD];
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			pL[n] = L(i, j, k, pg + n);
-			pR[n] = R(i, j, k, pg + n);
-			cL[n] = U(im, jm, km, RAD0 + pg + n);
-			cR[n] = U(i, j, k, RAD0 + pg + n);
-		}
+		loadRad(L, L.idx(i, j, k), pg, pL);
+		loadRad(R, R.idx(i, j, k), pg, pR);
+		loadRad(U, U.idx(i - unit(DIR, 0), j - unit(DIR, 1), k - unit(DIR, 2)), RAD0 + pg, cL);
+		loadRad(U, U.idx(i, j, k), RAD0 + pg, cR);
 		radFaceFlux<DIR>(rad, pL, pR, cL, cR, Fo, faceEpsilon(eps_t, b, i, j, k, static_cast<int>(blockIdx.z)));
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			F(i, j, k, pg + n) = Fo[n];
-		}
+		storeRad(F, F.idx(i, j, k), pg, Fo);
 	}, rad.ngroups);
-}
-
-// cons -> prim of one cell (radiation_system.hpp:603-610)
-QK_DEV void radPrim(Rad const &r, const double c[NRAD], double p[NRAD])
-{
-	p[0] = c[0];
-	const Recip RcE = recipOf(r.c * c[0]); // three quotients, one refined reciprocal (qk_device.hpp: same bits as three `/`)
-	p[1] = divBy(c[1], RcE);
-	p[2] = divBy(c[2], RcE);
-	p[3] = divBy(c[3], RcE);
 }
 
 template <int DIR, int ORDER> void launchRadFusedFlux(qk_level *lev, qk_stream s, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, const qk_array4 *eps_t)
@@ -86,55 +172,82 @@ template <int DIR, int ORDER> void launchRadFusedFlux(qk_level *lev, qk_stream s
 		WA4 F(flux_t[b]);
 		const int dx = unit(DIR, 0), dy = unit(DIR, 1), dz = unit(DIR, 2);
 		const int pg = NRAD * static_cast<int>(blockIdx.z); // component offset of this block's photon group
-		// cells i-3 .. i+2 along DIR
-		double c[6][NRAD], p[6][NRAD];
-		constexpr int M0 = (ORDER == 3) ? 0 : (ORDER == 2) ? 1 : 2;
-		constexpr int M1 = (ORDER == 3) ? 5 : (ORDER == 2) ? 4 : 3;
+		double c[6][NRAD], p[6][NRAD]; // cells i-3 .. i+2 along DIR
 #pragma unroll
-		for (int m = M0; m <= M1; ++m) {
-			const int64_t o = U.idx(i + (m - 3) * dx, j + (m - 3) * dy, k + (m - 3) * dz);
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				c[m][n] = U.p[o + U.ns * (RAD0 + pg + n)];
-			}
+		for (int m = RAD_M0<ORDER>; m <= RAD_M1<ORDER>; ++m) {
+			loadRad(U, U.idx(i + (m - 3) * dx, j + (m - 3) * dy, k + (m - 3) * dz), RAD0 + pg, c[m]);
 			radPrim(rad, c[m], p[m]);
 		}
 		double pL[NRAD], pR[NRAD], Fo[NRAD];
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			if (ORDER == 3) {
-				double am, ap;
-				ppmEdges(p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap); // cell i-1: right edge -> leftState(i)
-				pL[n] = ap;
-				ppmEdges(p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap); // cell i: left edge -> rightState(i)
-				pR[n] = am;
-			} else if (ORDER == 2) {
-				// hyperbolic_system.hpp:243-246 with the MC limiter (QuokkaSimulation.hpp:1948)
-				const double lslope = MC(p[3][n] - p[2][n], p[2][n] - p[1][n]);
-				const double rslope = MC(p[4][n] - p[3][n], p[3][n] - p[2][n]);
-				pL[n] = p[2][n] + 0.25 * lslope;
-				pR[n] = p[3][n] - 0.25 * rslope;
-			} else {
-				pL[n] = p[2][n];
-				pR[n] = p[3][n];
-			}
-		}
+		radFaceStates<ORDER>(p, pL, pR);
 		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(eps_t, b, i, j, k, static_cast<int>(blockIdx.z)));
-		const int64_t o = F.idx(i, j, k);
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			F.p[o + F.ns * (pg + n)] = Fo[n];
-		}
+		storeRad(F, F.idx(i, j, k), pg, Fo);
 	}, rad.ngroups);
 }
 
-// Y / Z sweeps: one thread marches a strip of STRIP faces along DIR with a rolling window of cells, so that every cell's primitives and
-// edge states are evaluated once per strip instead of once per face that touches it (the per-face kernel above is FP64-issue bound:
-// 4-6 cons->prim conversions and two reconstructions per face).  Same functions, same operands: identical fluxes.
+// Y / Z marches: one thread walks along DIR, face by face, with a rolling window of cells, so that every cell's primitives and edge states are
+// evaluated once per strip instead of once per face that touches it (the per-face kernel above is FP64-issue bound: 4-6 cons->prim conversions
+// and two reconstructions per face).  Same functions, same operands: identical fluxes.
+template <int DIR> struct RadPencil { // the thread's pencil along DIR
+	static_assert(DIR == 1 || DIR == 2, "marches: strided directions only");
+	int i, ot; // its x index and its index along the other strided direction
+	// (j, k) of cell or face n of the pencil, and its offset in X
+	QK_DEV auto j(int n) const -> int { return (DIR == 1) ? n : ot; }
+	QK_DEV auto k(int n) const -> int { return (DIR == 2) ? n : ot; }
+	template <class A> QK_DEV auto at(A const &X, int n) const -> int64_t { return X.idx(i, j(n), k(n)); }
+};
+template <int DIR, int ORDER> struct RadMarch { // the rolling window
+	static constexpr int M0 = RAD_M0<ORDER>, M1 = RAD_M1<ORDER>;
+	static constexpr int AHEAD = M1 - 3; // the cell that enters the window at a face is face + AHEAD
+	double c[6][NRAD], p[6][NRAD]; // cells face-3 .. face+2 along DIR (only M0..M1 are live)
+	double carry[NRAD];	       // PPM: right edge of cell face-1; PLM: its limited slope
+
+	// the window of the first face and the carry into it; comp0: the first component of the photon group in U
+	QK_DEV void start(Rad const &rad, RA4 const &U, RadPencil<DIR> const &pen, int comp0, int face)
+	{
+#pragma unroll
+		for (int m = M0; m <= M1; ++m) {
+			loadRad(U, pen.at(U, face + (m - 3)), comp0, c[m]);
+			radPrim(rad, c[m], p[m]);
+		}
+#pragma unroll
+		for (int n = 0; n < NRAD; ++n) {
+			carry[n] = radSeedCarry<ORDER>(p, n);
+		}
+	}
+	// on to the next face: `entering` is the conserved state of the cell AHEAD of it
+	QK_DEV void advance(Rad const &rad, const double entering[NRAD])
+	{
+#pragma unroll
+		for (int m = M0; m < M1; ++m) {
+#pragma unroll
+			for (int n = 0; n < NRAD; ++n) {
+				c[m][n] = c[m + 1][n];
+				p[m][n] = p[m + 1][n];
+			}
+		}
+#pragma unroll
+		for (int n = 0; n < NRAD; ++n) {
+			c[M1][n] = entering[n];
+		}
+		radPrim(rad, c[M1], p[M1]);
+	}
+	// the flux of photon group g at `face`, the face the window stands at
+	QK_DEV void flux(Rad const &rad, const qk_array4 *eps_t, int b, RadPencil<DIR> const &pen, int face, int g, double Fo[NRAD])
+	{
+		double pL[NRAD], pR[NRAD];
+#pragma unroll
+		for (int n = 0; n < NRAD; ++n) {
+			radStepFace<ORDER>(p, n, carry[n], pL[n], pR[n]);
+		}
+		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(eps_t, b, pen.i, pen.j(face), pen.k(face), g));
+	}
+};
+
+// fluxes only: strips of STRIP faces
 template <int DIR, int ORDER, int STRIP>
 __global__ void __launch_bounds__(256) k_rad_flux_march(const qk_box *boxes, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, int notb, const qk_array4 *eps_t)
 {
-	static_assert(DIR == 1 || DIR == 2, "marching flux kernel: strided directions only");
 	constexpr int OT = 3 - DIR;
 	const int b = static_cast<int>(blockIdx.z) / rad.ngroups;
 	const int pg = NRAD * (static_cast<int>(blockIdx.z) % rad.ngroups); // component offset of this block's photon group
@@ -148,113 +261,88 @@ __global__ void __launch_bounds__(256) k_rad_flux_march(const qk_box *boxes, Rad
 	}
 	RA4 U(cons_t[b]);
 	WA4 F(flux_t[b]);
-	constexpr int M0 = (ORDER == 3) ? 0 : (ORDER == 2) ? 1 : 2;
-	constexpr int M1 = (ORDER == 3) ? 5 : (ORDER == 2) ? 4 : 3;
-	double c[6][NRAD], p[6][NRAD]; // cells face-3 .. face+2 along DIR (only M0..M1 are live)
-	double carry[NRAD];	       // PPM: right edge of cell face-1; PLM: its limited slope
-	int pos[3];
-	pos[0] = i;
-	pos[OT] = ot;
-	auto load = [&](int m, int face) {
-		pos[DIR] = face + (m - 3);
-		const int64_t o = U.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			c[m][n] = U.p[o + U.ns * (RAD0 + pg + n)];
-		}
-		radPrim(rad, c[m], p[m]);
-	};
+	const RadPencil<DIR> pen{i, ot};
+	RadMarch<DIR, ORDER> w;
 	const int nface = min(STRIP, bx.hi[DIR] + 1 - f0 + 1);
 	for (int sI = 0; sI < nface; ++sI) {
 		const int face = f0 + sI;
 		if (sI == 0) {
-#pragma unroll
-			for (int m = M0; m <= M1; ++m) {
-				load(m, face);
-			}
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				if (ORDER == 3) {
-					double am, ap;
-					ppmEdges(p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap);
-					carry[n] = ap;
-				} else if (ORDER == 2) {
-					carry[n] = MC(p[3][n] - p[2][n], p[2][n] - p[1][n]);
-				}
-			}
+			w.start(rad, U, pen, RAD0 + pg, face);
 		} else {
-#pragma unroll
-			for (int m = M0; m < M1; ++m) {
-#pragma unroll
-				for (int n = 0; n < NRAD; ++n) {
-					c[m][n] = c[m + 1][n];
-					p[m][n] = p[m + 1][n];
-				}
-			}
-			load(M1, face);
+			double entering[NRAD];
+			loadRad(U, pen.at(U, face + w.AHEAD), RAD0 + pg, entering);
+			w.advance(rad, entering);
 		}
-		double pL[NRAD], pR[NRAD], Fo[NRAD];
+		double Fo[NRAD];
+		w.flux(rad, eps_t, b, pen, face, pg / NRAD, Fo);
+		storeRad(F, pen.at(F, face), pg, Fo);
+	}
+}
+
+// X slab: one thread per cell of a flat slab (rows j = lo.y .. hi.y of plane k are contiguous, ghost cells included), primitives and
+// edge states exchanged through LDS, each thread evaluates the flux at the left face of its cell: one cons->prim and one reconstruction per
+// cell instead of 4-6 and 2 per face.  250 faces per 256-thread workgroup (3 halo cells on each side).  Same functions, same operands.
+constexpr int RXB = 256, RXOUT = 250;
+constexpr int RXCELLS = RXB - 7; // cells updated per workgroup of the X sweep: threads 3 .. RXB-4 (their right neighbour holds the other face)
+
+// edge pass of lane t: the left edge state of its cell (= the right state of its left face) and, into s_e, what the cell gives to its right face
+template <int ORDER> QK_DEV void radEdgePass(const double (*s_p)[RXB], double (*s_e)[RXB], int t, const double p0[NRAD], double edgeL[NRAD])
+{
+	const int tm2 = max(t - 2, 0), tm1 = max(t - 1, 0), tp1 = min(t + 1, RXB - 1), tp2 = min(t + 2, RXB - 1);
 #pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			if (ORDER == 3) {
-				double am, ap;
-				ppmEdges(p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap); // cell `face`
-				pL[n] = carry[n];
-				pR[n] = am;
-				carry[n] = ap;
-			} else if (ORDER == 2) {
-				const double rslope = MC(p[4][n] - p[3][n], p[3][n] - p[2][n]); // slope of cell `face`
-				pL[n] = p[2][n] + 0.25 * carry[n];
-				pR[n] = p[3][n] - 0.25 * rslope;
-				carry[n] = rslope;
-			} else {
-				pL[n] = p[2][n];
-				pR[n] = p[3][n];
-			}
+	for (int n = 0; n < NRAD; ++n) {
+		if constexpr (ORDER == 3) {
+			double am, ap;
+			ppmEdges(s_p[n][tm2], s_p[n][tm1], p0[n], s_p[n][tp1], s_p[n][tp2], am, ap);
+			edgeL[n] = am;
+			s_e[n][t] = ap;
+		} else if constexpr (ORDER == 2) {
+			const double slope = MC(s_p[n][tp1] - p0[n], p0[n] - s_p[n][tm1]);
+			edgeL[n] = p0[n] - 0.25 * slope;
+			s_e[n][t] = slope;
+		} else {
+			edgeL[n] = p0[n];
 		}
-		pos[DIR] = face;
-		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(eps_t, b, pos[0], pos[1], pos[2], pg / NRAD));
-		const int64_t o = F.idx(pos[0], pos[1], pos[2]);
+	}
+}
+// the left state of a lane's left face, gathered from its left neighbour's lane tm1
+template <int ORDER> QK_DEV void radLeftState(const double (*s_p)[RXB], const double (*s_e)[RXB], int tm1, double pL[NRAD])
+{
 #pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			F.p[o + F.ns * (pg + n)] = Fo[n];
+	for (int n = 0; n < NRAD; ++n) {
+		if constexpr (ORDER == 3) {
+			pL[n] = s_e[n][tm1];
+		} else if constexpr (ORDER == 2) {
+			pL[n] = s_p[n][tm1] + 0.25 * s_e[n][tm1];
+		} else {
+			pL[n] = s_p[n][tm1];
 		}
 	}
 }
 
-// X sweep: one thread per cell of a flat slab (rows j = lo.y .. hi.y of plane k are contiguous, ghost cells included), primitives and
-// edge states exchanged through LDS, each thread evaluates the flux at the left face of its cell: one cons->prim and one reconstruction per
-// cell instead of 4-6 and 2 per face.  250 faces per 256-thread workgroup (3 halo cells on each side).  Same functions, same operands.
-constexpr int RXB = 256, RXOUT = 250;
-
-template <int ORDER> __global__ void __launch_bounds__(RXB) k_rad_flux_x(const qk_box *boxes, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, const qk_array4 *eps_t)
+struct RadXLane {
+	int i, j;    // the lane's cell in plane k
+	bool isFace; // its left face is a face of the box and this workgroup's to evaluate: Fo holds the flux there
+};
+// The slab body up to the flux at the lane's left face.  Workgroup blockIdx.x starts STEP slab positions after its predecessor.
+template <int ORDER, int STEP>
+QK_DEV auto radXSlabFlux(Rad const &rad, qk_box const &bx, int b, int k, const qk_array4 *cons_t, int pg, const qk_array4 *eps_t, double Fo[NRAD]) -> RadXLane
 {
 	__shared__ double s_p[NRAD][RXB]; // primitives
 	__shared__ double s_e[NRAD][RXB]; // PPM: right edge a_plus of the cell; PLM: its limited slope
 	__shared__ double s_c[NRAD][RXB]; // conserved radiation state (the first-order fallback of the HLL flux needs it)
-	const int b = static_cast<int>(blockIdx.z) / rad.ngroups;
-	const int pg = NRAD * (static_cast<int>(blockIdx.z) % rad.ngroups); // component offset of this block's photon group
-	const qk_box bx = boxes[b];
-	const int k = bx.lo[2] + static_cast<int>(blockIdx.y);
-	if (k > bx.hi[2]) {
-		return; // uniform for the workgroup
-	}
 	RA4 U(cons_t[b]);
 	const int t = threadIdx.x;
 	const int64_t rowlen = cons_t[b].end[0] - cons_t[b].begin[0]; // x extent of the array, ghost cells included (the row PITCH, U.js, may be larger)
 	const int64_t slablen = rowlen * (bx.hi[1] - bx.lo[1] + 1);
-	const int64_t f = static_cast<int64_t>(blockIdx.x) * RXOUT + t - 3; // flat position inside the slab of plane k
+	const int64_t f = static_cast<int64_t>(blockIdx.x) * STEP + t - 3; // flat position inside the slab of plane k
 	const bool inside = (f >= 0) && (f < slablen);
 	const int64_t fc = inside ? f : 0;
 	const int jj = static_cast<int>(fc / rowlen);
 	const int i = U.bx + static_cast<int>(fc - jj * rowlen);
 	const int j = bx.lo[1] + jj;
-	const int64_t o = U.idx(i, j, k);
 	double c0[NRAD], p0[NRAD];
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		c0[n] = U.p[o + U.ns * (RAD0 + pg + n)];
-	}
+	loadRad(U, U.idx(i, j, k), RAD0 + pg, c0);
 	radPrim(rad, c0, p0);
 #pragma unroll
 	for (int n = 0; n < NRAD; ++n) {
@@ -262,47 +350,54 @@ template <int ORDER> __global__ void __launch_bounds__(RXB) k_rad_flux_x(const q
 		s_p[n][t] = p0[n];
 	}
 	__syncthreads();
-	const int tm2 = max(t - 2, 0), tm1 = max(t - 1, 0), tp1 = min(t + 1, RXB - 1), tp2 = min(t + 2, RXB - 1);
-	double edgeL[NRAD]; // left edge state of my cell = rightState of my left face
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		if (ORDER == 3) {
-			double am, ap;
-			ppmEdges(s_p[n][tm2], s_p[n][tm1], p0[n], s_p[n][tp1], s_p[n][tp2], am, ap);
-			edgeL[n] = am;
-			s_e[n][t] = ap;
-		} else if (ORDER == 2) {
-			const double slope = MC(s_p[n][tp1] - p0[n], p0[n] - s_p[n][tm1]); // hyperbolic_system.hpp:243-246, MC limiter
-			edgeL[n] = p0[n] - 0.25 * slope;
-			s_e[n][t] = slope;
-		} else {
-			edgeL[n] = p0[n];
-		}
-	}
+	double edgeL[NRAD];
+	radEdgePass<ORDER>(s_p, s_e, t, p0, edgeL);
 	__syncthreads();
 	const bool isFace = inside && (i >= bx.lo[0]) && (i <= bx.hi[0] + 1) && (t >= 3) && (t <= RXB - 3);
 	if (!isFace) {
+		return {i, j, false};
+	}
+	double pL[NRAD], cL[NRAD];
+#pragma unroll
+	for (int n = 0; n < NRAD; ++n) {
+		cL[n] = s_c[n][t - 1];
+	}
+	radLeftState<ORDER>(s_p, s_e, t - 1, pL);
+	radFaceFlux<0>(rad, pL, edgeL, cL, c0, Fo, faceEpsilon(eps_t, b, i, j, k, pg / NRAD));
+	return {i, j, true};
+}
+
+template <int ORDER> __global__ void __launch_bounds__(RXB) k_rad_flux_x(const qk_box *boxes, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, const qk_array4 *eps_t)
+{
+	const int b = static_cast<int>(blockIdx.z) / rad.ngroups;
+	const int pg = NRAD * (static_cast<int>(blockIdx.z) % rad.ngroups); // component offset of this block's photon group
+	const qk_box bx = boxes[b];
+	const int k = bx.lo[2] + static_cast<int>(blockIdx.y);
+	if (k > bx.hi[2]) {
+		return; // uniform for the workgroup
+	}
+	double Fo[NRAD];
+	const RadXLane me = radXSlabFlux<ORDER, RXOUT>(rad, bx, b, k, cons_t, pg, eps_t, Fo);
+	if (!me.isFace) {
 		return;
 	}
-	double pL[NRAD], cL[NRAD], Fo[NRAD];
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		cL[n] = s_c[n][tm1];
-		if (ORDER == 3) {
-			pL[n] = s_e[n][tm1];
-		} else if (ORDER == 2) {
-			pL[n] = s_p[n][tm1] + 0.25 * s_e[n][tm1];
-		} else {
-			pL[n] = s_p[n][tm1];
-		}
-	}
-	radFaceFlux<0>(rad, pL, edgeL, cL, c0, Fo, faceEpsilon(eps_t, b, i, j, k, pg / NRAD));
 	WA4 F(flux_t[b]);
-	const int64_t of = F.idx(i, j, k);
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		F.p[of + F.ns * (pg + n)] = Fo[n];
-	}
+	storeRad(F, F.idx(me.i, me.j, k), pg, Fo);
+}
+
+// grid of an X-slab kernel whose workgroups advance by `step` positions, over nz boxes (x photon groups)
+auto radXSlabGrid(const qk_level *lev, int nghost, int step, int nz) -> dim3
+{
+	const int64_t slab = static_cast<int64_t>(lev->maxlen[0] + 2 * nghost) * lev->maxlen[1];
+	return dim3(static_cast<unsigned>((slab + step - 1) / step), static_cast<unsigned>(lev->maxlen[2]), static_cast<unsigned>(nz));
+}
+// grid of a march along dir that covers `len` cells or faces of a pencil in strips of `strip`: 64 x 4 pencils per workgroup, notb workgroups
+// across the other strided direction for each strip
+auto radMarchGrid(const qk_level *lev, int dir, int len, int strip, int nz, int &notb) -> dim3
+{
+	notb = (lev->maxlen[3 - dir] + 3) / 4;
+	const int nstrips = (len + strip - 1) / strip;
+	return dim3((lev->maxlen[0] + 63) / 64, notb * nstrips, nz);
 }
 
 template <int ORDER> void launchRadXFlux(qk_level *lev, qk_stream s, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, int nghost, const qk_array4 *eps_t)
@@ -310,11 +405,9 @@ template <int ORDER> void launchRadXFlux(qk_level *lev, qk_stream s, Rad rad, co
 	if (lev->nboxes == 0) {
 		return;
 	}
-	const int64_t slab = static_cast<int64_t>(lev->maxlen[0] + 2 * nghost) * lev->maxlen[1];
-	const dim3 grid(static_cast<unsigned>((slab + RXOUT - 1) / RXOUT), static_cast<unsigned>(lev->maxlen[2]),
-			static_cast<unsigned>(lev->nboxes * rad.ngroups));
 	ProfScope ps(lev->ctx, static_cast<hipStream_t>(s), "rad_fluxFunction");
-	hipLaunchKernelGGL((k_rad_flux_x<ORDER>), grid, dim3(RXB), 0, static_cast<hipStream_t>(s), lev->d_boxes, rad, cons_t, flux_t, eps_t);
+	hipLaunchKernelGGL((k_rad_flux_x<ORDER>), radXSlabGrid(lev, nghost, RXOUT, lev->nboxes * rad.ngroups), dim3(RXB), 0, static_cast<hipStream_t>(s), lev->d_boxes, rad,
+			   cons_t, flux_t, eps_t);
 }
 
 template <int DIR, int ORDER> void launchRadMarchFlux(qk_level *lev, qk_stream s, Rad rad, const qk_array4 *cons_t, qk_array4 *flux_t, const qk_array4 *eps_t)
@@ -323,14 +416,37 @@ template <int DIR, int ORDER> void launchRadMarchFlux(qk_level *lev, qk_stream s
 		return;
 	}
 	constexpr int STRIP = 8;
-	constexpr int OT = 3 - DIR;
-	const int notb = (lev->maxlen[OT] + 3) / 4;
-	const int nstrips = (lev->maxlen[DIR] + 1 + STRIP - 1) / STRIP;
-	const dim3 grid((lev->maxlen[0] + 63) / 64, notb * nstrips, lev->nboxes * rad.ngroups);
+	int notb;
+	const dim3 grid = radMarchGrid(lev, DIR, lev->maxlen[DIR] + 1, STRIP, lev->nboxes * rad.ngroups, notb);
 	ProfScope ps(lev->ctx, static_cast<hipStream_t>(s), "rad_fluxFunction");
 	hipLaunchKernelGGL((k_rad_flux_march<DIR, ORDER, STRIP>), grid, dim3(64, 4), 0, static_cast<hipStream_t>(s), lev->d_boxes, rad, cons_t, flux_t, notb, eps_t);
 }
 
+// isStateValid is a property of the whole cell (radiation_system.hpp:626-644: every group), amendRadState then repairs every group (:646-665: a
+// valid group below its floor is lifted as well).  update(pg, cons) forms the new state of one group; several groups: one pass for the verdict,
+// one to store (U_new may alias what update reads: nothing is stored before the verdict).  o = Un.idx(i, j, k).
+template <class F> QK_DEV void updateRadGroups(Rad const &rad, WA4 const &Un, int64_t o, F const &update)
+{
+	bool cellValid = true;
+	double cons[NRAD];
+	if (rad.ngroups > 1) {
+		for (int g = 0; g < rad.ngroups; ++g) {
+			update(NRAD * g, cons);
+			cellValid = cellValid && radStateValid(rad, cons);
+		}
+	}
+	for (int g = 0; g < rad.ngroups; ++g) {
+		const int pg = NRAD * g;
+		update(pg, cons);
+		if (rad.ngroups == 1) {
+			cellValid = radStateValid(rad, cons);
+		}
+		if (!cellValid) {
+			amendRadState(rad, cons);
+		}
+		storeRad(Un, o, RAD0 + pg, cons);
+	}
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // One transport stage without the face-flux round trip (qk_rad_stage_fused): the flux kernels above with the flux divergence taken where the
@@ -348,53 +464,8 @@ struct RadSweep {
 	int pg; // component offset of the photon group these launches advance (NRAD * group): the groups are transported independently of each other
 };
 
-// Non-temporal hints on the flux-divergence accumulator of the fused transport stage where they pay: the X sweep's stores and the Z sweep's loads
-// (same box: Z -3.5 %, X -1.5 %).  The Y sweep, which reads AND rewrites the accumulator, is 5 % slower with them and keeps plain accesses.
-// Level 2 (default) adds the Z sweep's stores of the new radiation state and its loads of the substep's starting state (Z another -2 %).  QK_RAD_NT=0: none.
-#ifndef QK_RAD_NT
-#define QK_RAD_NT 2
-#endif
-template <class P> QK_DEV void radStreamStore(P *p, double v)
-{
-#if QK_RAD_NT
-	__builtin_nontemporal_store(v, p);
-#else
-	*p = v;
-#endif
-}
-template <class P> QK_DEV auto radStreamLoad(P *p) -> double
-{
-#if QK_RAD_NT
-	return __builtin_nontemporal_load(p);
-#else
-	return *p;
-#endif
-}
-
-template <class P> QK_DEV void radStreamStore2(P *p, double v)
-{
-#if QK_RAD_NT >= 2
-	__builtin_nontemporal_store(v, p);
-#else
-	*p = v;
-#endif
-}
-template <class P> QK_DEV auto radStreamLoad2(P *p) -> double
-{
-#if QK_RAD_NT >= 2
-	return __builtin_nontemporal_load(p);
-#else
-	return *p;
-#endif
-}
-
-constexpr int RXCELLS = RXB - 7; // cells updated per workgroup of the X sweep: threads 3 .. RXB-4 (their right neighbour holds the other face)
-
 template <int ORDER, bool STORE> __global__ void __launch_bounds__(RXB) k_rad_sweep_x(const qk_box *boxes, Rad rad, RadSweep a)
 {
-	__shared__ double s_p[NRAD][RXB];
-	__shared__ double s_e[NRAD][RXB];
-	__shared__ double s_c[NRAD][RXB];
 	__shared__ double s_f[NRAD][RXB]; // flux at the left face of the thread's cell
 	const int b = static_cast<int>(blockIdx.z); // (no XCD-contiguous remap: measured 5 % slower here, qk_device.hpp)
 	const qk_box bx = boxes[b];
@@ -402,96 +473,39 @@ template <int ORDER, bool STORE> __global__ void __launch_bounds__(RXB) k_rad_sw
 	if (k > bx.hi[2]) {
 		return; // uniform for the workgroup
 	}
-	RA4 U(a.U_in[b]);
+	double Fo[NRAD];
+	const RadXLane me = radXSlabFlux<ORDER, RXCELLS>(rad, bx, b, k, a.U_in, a.pg, a.eps[0], Fo);
 	const int t = threadIdx.x;
-	const int64_t rowlen = a.U_in[b].end[0] - a.U_in[b].begin[0]; // cells of a row, ghost cells included (not the row pitch U.js)
-	const int64_t slablen = rowlen * (bx.hi[1] - bx.lo[1] + 1);
-	const int64_t f = static_cast<int64_t>(blockIdx.x) * RXCELLS + t - 3;
-	const bool inside = (f >= 0) && (f < slablen);
-	const int64_t fc = inside ? f : 0;
-	const int jj = static_cast<int>(fc / rowlen);
-	const int i = U.bx + static_cast<int>(fc - jj * rowlen);
-	const int j = bx.lo[1] + jj;
-	const int64_t o = U.idx(i, j, k);
-	double c0[NRAD], p0[NRAD];
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		c0[n] = U.p[o + U.ns * (RAD0 + a.pg + n)];
-	}
-	radPrim(rad, c0, p0);
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		s_c[n][t] = c0[n];
-		s_p[n][t] = p0[n];
-	}
-	__syncthreads();
-	const int tm2 = max(t - 2, 0), tm1 = max(t - 1, 0), tp1 = min(t + 1, RXB - 1), tp2 = min(t + 2, RXB - 1);
-	double edgeL[NRAD];
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		if (ORDER == 3) {
-			double am, ap;
-			ppmEdges(s_p[n][tm2], s_p[n][tm1], p0[n], s_p[n][tp1], s_p[n][tp2], am, ap);
-			edgeL[n] = am;
-			s_e[n][t] = ap;
-		} else if (ORDER == 2) {
-			const double slope = MC(s_p[n][tp1] - p0[n], p0[n] - s_p[n][tm1]);
-			edgeL[n] = p0[n] - 0.25 * slope;
-			s_e[n][t] = slope;
-		} else {
-			edgeL[n] = p0[n];
-		}
-	}
-	__syncthreads();
-	const bool isFace = inside && (i >= bx.lo[0]) && (i <= bx.hi[0] + 1) && (t >= 3) && (t <= RXB - 3);
-	double Fo[NRAD] = {0.0, 0.0, 0.0, 0.0};
-	if (isFace) {
-		double pL[NRAD], cL[NRAD];
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			cL[n] = s_c[n][tm1];
-			if (ORDER == 3) {
-				pL[n] = s_e[n][tm1];
-			} else if (ORDER == 2) {
-				pL[n] = s_p[n][tm1] + 0.25 * s_e[n][tm1];
-			} else {
-				pL[n] = s_p[n][tm1];
-			}
-		}
-		radFaceFlux<0>(rad, pL, edgeL, cL, c0, Fo, faceEpsilon(a.eps[0], b, i, j, k, a.pg / NRAD));
+	if (me.isFace) {
 #pragma unroll
 		for (int n = 0; n < NRAD; ++n) {
 			s_f[n][t] = Fo[n];
 		}
 	}
 	__syncthreads();
-	if (!isFace || t > RXB - 4) {
+	if (!me.isFace || t > RXB - 4) {
 		return;
 	}
 	if (STORE) {
 		WA4 F(a.flux[0][b]);
-		const int64_t of = F.idx(i, j, k);
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			F.p[of + F.ns * (a.pg + n)] = Fo[n];
-		}
+		storeRad(F, F.idx(me.i, me.j, k), a.pg, Fo);
 	}
-	if (i <= bx.hi[0]) { // a cell of the box: its right face is the next thread's
+	if (me.i <= bx.hi[0]) { // a cell of the box: its right face is the next thread's
 		WA4 A(a.acc[b]);
-		const int64_t oa = A.idx(i, j, k);
+		double d[NRAD];
 #pragma unroll
 		for (int n = 0; n < NRAD; ++n) {
-			radStreamStore(&A.p[oa + A.ns * (a.pg + n)], a.dtdx[0] * (Fo[n] - s_f[n][t + 1]));
+			d[n] = a.dtdx[0] * (Fo[n] - s_f[n][t + 1]);
 		}
+		storeRadNT(A, A.idx(me.i, me.j, k), a.pg, d); // (written once, read next by another kernel: non-temporal)
 	}
 }
 
-// Y and Z sweeps: one thread marches `strip` cells of a pencil along DIR (strip + 1 faces) with the rolling window of k_rad_flux_march.
+// Y and Z sweeps: one thread marches `strip` cells of a pencil along DIR (strip + 1 faces).
 // EPI 0: acc += term (Y); 1: PredictStep update; 2: AddFluxesRK2 update (Z; the strip is the whole pencil then, see RadSweep::U_new).
 template <int DIR, int ORDER, int EPI, bool STORE>
 __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Rad rad, RadSweep a, int notb, int strip)
 {
-	static_assert(DIR == 1 || DIR == 2, "marching sweep: strided directions only");
 	static_assert((0.5 - IMEX_a32) == 0.0, "the fused stage drops the old-state fluxes of AddFluxesRK2: PD-ARS only");
 	constexpr int OT = 3 - DIR;
 	const BlockId blk = xcdContiguousBlock(); // (the two chunks of a row, and consecutive rows, share cache lines: qk_device.hpp)
@@ -517,117 +531,42 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 		}
 	}
 	RA4 U(a.U_in[b]);
-	constexpr int M0 = (ORDER == 3) ? 0 : (ORDER == 2) ? 1 : 2;
-	constexpr int M1 = (ORDER == 3) ? 5 : (ORDER == 2) ? 4 : 3;
-	double c[6][NRAD], p[6][NRAD];
-	double carry[NRAD];
+	WA4 A(a.acc[b]);
+	const RadPencil<DIR> pen{i, ot};
+	RadMarch<DIR, ORDER> w;
 	double Fprev[NRAD];
 	double nextc[NRAD]; // the cell that enters the window at the next face: loaded one face ahead, so that its latency hides behind a flux
 	double accv[NRAD];  // accumulator of the cell that is completed at this face: loaded before the flux, used after it
 	double u0v[NRAD];   // (Z) and its state at the start of the substep
-	int pos[3];
-	pos[0] = i;
-	pos[OT] = ot;
-	WA4 A(a.acc[b]);
-	auto loadCons = [&](int cell, double out[NRAD]) {
-		pos[DIR] = cell;
-		const int64_t o = U.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			out[n] = U.p[o + U.ns * (RAD0 + a.pg + n)];
-		}
-	};
-#pragma unroll
-	for (int m = M0; m <= M1; ++m) {
-		loadCons(c0 + (m - 3), c[m]);
-		radPrim(rad, c[m], p[m]);
-	}
-#pragma unroll
-	for (int n = 0; n < NRAD; ++n) {
-		if (ORDER == 3) {
-			double am, ap;
-			ppmEdges(p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap);
-			carry[n] = ap;
-		} else if (ORDER == 2) {
-			carry[n] = MC(p[3][n] - p[2][n], p[2][n] - p[1][n]);
-		}
-	}
+	w.start(rad, U, pen, RAD0 + a.pg, c0);
 	for (int face = c0; face <= c1 + 1; ++face) {
 		if (face > c0) {
-#pragma unroll
-			for (int m = M0; m < M1; ++m) {
-#pragma unroll
-				for (int n = 0; n < NRAD; ++n) {
-					c[m][n] = c[m + 1][n];
-					p[m][n] = p[m + 1][n];
-				}
-			}
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				c[M1][n] = nextc[n];
-			}
-			radPrim(rad, c[M1], p[M1]);
-			pos[DIR] = face - 1;
-			const int64_t oa = A.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				accv[n] = (EPI == 0) ? A.p[oa + A.ns * (a.pg + n)] : radStreamLoad(&A.p[oa + A.ns * (a.pg + n)]);
-			}
-			if (EPI != 0) {
+			w.advance(rad, nextc);
+			if (EPI == 0) {
+				loadRad(A, pen.at(A, face - 1), a.pg, accv); // (Y reads AND rewrites the accumulator: plain accesses)
+			} else {
 				RA4 Uo(a.U0[b]);
-				const int64_t oo = Uo.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-				for (int n = 0; n < NRAD; ++n) {
-					u0v[n] = radStreamLoad2(&Uo.p[oo + Uo.ns * (RAD0 + a.pg + n)]);
-				}
+				loadRadNT(A, pen.at(A, face - 1), a.pg, accv); // (Z: the accumulator's last use, and the only use of U0 — non-temporal)
+				loadRadNT(Uo, pen.at(Uo, face - 1), RAD0 + a.pg, u0v);
 			}
 		}
 		if (face <= c1) {
-			loadCons(face + 1 + (M1 - 3), nextc); // (ahead of every cell this thread writes)
+			loadRad(U, pen.at(U, face + 1 + w.AHEAD), RAD0 + a.pg, nextc); // (ahead of every cell this thread writes)
 		}
-		double pL[NRAD], pR[NRAD], Fo[NRAD];
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			if (ORDER == 3) {
-				double am, ap;
-				ppmEdges(p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap);
-				pL[n] = carry[n];
-				pR[n] = am;
-				carry[n] = ap;
-			} else if (ORDER == 2) {
-				const double rslope = MC(p[4][n] - p[3][n], p[3][n] - p[2][n]);
-				pL[n] = p[2][n] + 0.25 * carry[n];
-				pR[n] = p[3][n] - 0.25 * rslope;
-				carry[n] = rslope;
-			} else {
-				pL[n] = p[2][n];
-				pR[n] = p[3][n];
-			}
-		}
-		pos[DIR] = face;
-		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(a.eps[DIR], b, pos[0], pos[1], pos[2], a.pg / NRAD));
+		double Fo[NRAD];
+		w.flux(rad, a.eps[DIR], b, pen, face, a.pg / NRAD, Fo);
 		if (STORE && (face <= c1 || c1 == bx.hi[DIR])) { // (the face after the strip belongs to the next strip, except at the end of the pencil)
 			WA4 F(a.flux[DIR][b]);
-			pos[DIR] = face;
-			const int64_t of = F.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				F.p[of + F.ns * (a.pg + n)] = Fo[n];
-			}
+			storeRad(F, pen.at(F, face), a.pg, Fo);
 		}
 		if (face > c0) { // cell face-1 has both its faces now
-			pos[DIR] = face - 1;
 			double cons[NRAD];
 #pragma unroll
 			for (int n = 0; n < NRAD; ++n) {
 				cons[n] = accv[n] + a.dtdx[DIR] * (Fprev[n] - Fo[n]);
 			}
 			if (EPI == 0) {
-				const int64_t oa = A.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-				for (int n = 0; n < NRAD; ++n) {
-					A.p[oa + A.ns * (a.pg + n)] = cons[n];
-				}
+				storeRad(A, pen.at(A, face - 1), a.pg, cons);
 			} else {
 #pragma unroll
 				for (int n = 0; n < NRAD; ++n) {
@@ -635,7 +574,7 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 						cons[n] = u0v[n] + cons[n]; // radiation_system.hpp:681-690
 					} else {
 						const double U_0 = u0v[n];
-						const double U_1 = c[2][n]; // the cell left of this face: still in the window
+						const double U_1 = w.c[2][n]; // the cell left of this face: still in the window
 						cons[n] = (1.0 - IMEX_a32) * U_0 + IMEX_a32 * U_1 + (0.5 * (cons[n])); // :758-759 with the zero-weight term dropped
 					}
 				}
@@ -643,11 +582,7 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 					amendRadState(rad, cons);
 				}
 				WA4 Un(a.U_new[b]);
-				const int64_t on = Un.idx(pos[0], pos[1], pos[2]);
-#pragma unroll
-				for (int n = 0; n < NRAD; ++n) {
-					radStreamStore2(&Un.p[on + Un.ns * (RAD0 + a.pg + n)], cons[n]);
-				}
+				storeRadNT(Un, pen.at(Un, face - 1), RAD0 + a.pg, cons); // (the new state is not read again by this stage: non-temporal)
 			}
 		}
 #pragma unroll
@@ -657,38 +592,43 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 	}
 }
 
-template <int ORDER, int STAGE, bool STORE> void launchRadSweeps(qk_level *lev, qk_stream s, Rad rad, RadSweep const &a, int nghost)
+// the three sweeps of one photon group (a.pg)
+template <int ORDER, int STAGE> void launchRadSweeps(qk_level *lev, qk_stream s, Rad rad, RadSweep const &a, int nghost, bool store)
 {
 	if (lev->nboxes == 0) {
 		return;
 	}
 	auto const st = static_cast<hipStream_t>(s);
-	{
-		const int64_t slab = static_cast<int64_t>(lev->maxlen[0] + 2 * nghost) * lev->maxlen[1];
-		const dim3 grid(static_cast<unsigned>((slab + RXCELLS - 1) / RXCELLS), static_cast<unsigned>(lev->maxlen[2]), static_cast<unsigned>(lev->nboxes));
-		ProfScope ps(lev->ctx, st, "rad_sweep_x");
-		hipLaunchKernelGGL((k_rad_sweep_x<ORDER, STORE>), grid, dim3(RXB), 0, st, lev->d_boxes, rad, a);
-	}
-	{
-		constexpr int STRIP = 16;
-		const int notb = (lev->maxlen[2] + 3) / 4;
-		const int nstrips = (lev->maxlen[1] + STRIP - 1) / STRIP;
-		const dim3 grid((lev->maxlen[0] + 63) / 64, notb * nstrips, lev->nboxes);
-		ProfScope ps(lev->ctx, st, "rad_sweep_y");
-		hipLaunchKernelGGL((k_rad_sweep_march<1, ORDER, 0, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, STRIP);
-	}
-	{
-		// written in place (stage 2 of the drivers: U_new is U_in), a pencil is one thread's: the cells behind its march are the only ones it
-		// has overwritten.  Otherwise strips, for more waves in flight.
-		// (Aliasing cannot be seen from the table POINTERS alone — two tables may describe the same storage, e.g. a sub-level's gathered
-		// descriptors.  Stage 2, the stage the drivers run in place, always marches whole pencils; stage 1 does when the tables are the same —
-		// and when two tables over one storage reach the kernel after all, it sees the equal fab pointers and falls back to whole pencils itself.)
-		const int strip = (STAGE == 2 || a.U_new == a.U_in) ? lev->maxlen[2] : 32;
-		const int notb = (lev->maxlen[1] + 3) / 4;
-		const int nstrips = (lev->maxlen[2] + strip - 1) / strip;
-		const dim3 grid((lev->maxlen[0] + 63) / 64, notb * nstrips, lev->nboxes);
-		ProfScope ps(lev->ctx, st, "rad_sweep_z");
-		hipLaunchKernelGGL((k_rad_sweep_march<2, ORDER, STAGE, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, strip);
+	auto sweeps = [&](auto storeFluxes) {
+		constexpr bool STORE = decltype(storeFluxes)::value;
+		{
+			ProfScope ps(lev->ctx, st, "rad_sweep_x");
+			hipLaunchKernelGGL((k_rad_sweep_x<ORDER, STORE>), radXSlabGrid(lev, nghost, RXCELLS, lev->nboxes), dim3(RXB), 0, st, lev->d_boxes, rad, a);
+		}
+		{
+			constexpr int STRIP = 16;
+			int notb;
+			const dim3 grid = radMarchGrid(lev, 1, lev->maxlen[1], STRIP, lev->nboxes, notb);
+			ProfScope ps(lev->ctx, st, "rad_sweep_y");
+			hipLaunchKernelGGL((k_rad_sweep_march<1, ORDER, 0, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, STRIP);
+		}
+		{
+			// written in place (stage 2 of the drivers: U_new is U_in), a pencil is one thread's: the cells behind its march are the only ones it
+			// has overwritten.  Otherwise strips, for more waves in flight.
+			// (Aliasing cannot be seen from the table POINTERS alone — two tables may describe the same storage, e.g. a sub-level's gathered
+			// descriptors.  Stage 2, the stage the drivers run in place, always marches whole pencils; stage 1 does when the tables are the same —
+			// and when two tables over one storage reach the kernel after all, it sees the equal fab pointers and falls back to whole pencils itself.)
+			const int strip = (STAGE == 2 || a.U_new == a.U_in) ? lev->maxlen[2] : 32;
+			int notb;
+			const dim3 grid = radMarchGrid(lev, 2, lev->maxlen[2], strip, lev->nboxes, notb);
+			ProfScope ps(lev->ctx, st, "rad_sweep_z");
+			hipLaunchKernelGGL((k_rad_sweep_march<2, ORDER, STAGE, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, strip);
+		}
+	};
+	if (store) {
+		sweeps(std::true_type{});
+	} else {
+		sweeps(std::false_type{});
 	}
 }
 
@@ -714,15 +654,9 @@ int qk_rad_ConservedToPrimitive(qk_level *lev, qk_stream s, const qk_rad_traits 
 		WA4 P(prim_t[b]);
 		const int pg = NRAD * static_cast<int>(blockIdx.z); // component offset of this block's photon group
 		double c[NRAD], p[NRAD];
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			c[n] = U(i, j, k, RAD0 + pg + n);
-		}
+		loadRad(U, U.idx(i, j, k), RAD0 + pg, c);
 		radPrim(rad, c, p);
-#pragma unroll
-		for (int n = 0; n < NRAD; ++n) {
-			P(i, j, k, pg + n) = p[n];
-		}
+		storeRad(P, P.idx(i, j, k), pg, p);
 	}, rad.ngroups);
 	return radStatus(lev, "rad ConservedToPrimitive");
 }
@@ -769,43 +703,20 @@ int qk_rad_computeRadiationFluxes(qk_level *lev, qk_stream s, const qk_rad_trait
 	QK_REQUIRE(lev->ctx, order >= 1 && order <= 3, "computeRadiationFluxes: reconstruction order must be 1..3");
 	QK_REQUIRE(lev->ctx, ndim == lev->ndim, "computeRadiationFluxes: ndim mismatch");
 	const Rad rad(*rt);
-#define QK_RAD_DIR(D)                                                                                                                                \
-	if (order == 3) {                                                                                                                            \
-		launchRadFusedFlux<D, 3>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	} else if (order == 2) {                                                                                                                     \
-		launchRadFusedFlux<D, 2>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	} else {                                                                                                                                     \
-		launchRadFusedFlux<D, 1>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	}
 	// 2-D builds: the radiation fluxes do not permute components with the direction (radiation_system.hpp:1026-1040), so the X2 view of
 	// ArrayView_2d.hpp and the cyclic one of the 3-D build address the same cells: the 3-D kernels on a single plane.
-	if (ndim >= 2) { // (state arrays carry nghost_cc = 4 ghost cells throughout the library; the slab below is sized for that)
-		if (order == 3) {
-			launchRadXFlux<3>(lev, s, rad, cons_t, flux[0], 4, eps[0]);
-		} else if (order == 2) {
-			launchRadXFlux<2>(lev, s, rad, cons_t, flux[0], 4, eps[0]);
+	dispatchConst1to3(order, [&](auto O) {
+		constexpr int ORDER = decltype(O)::value;
+		if (ndim >= 2) { // (state arrays carry nghost_cc = 4 ghost cells throughout the library; the slab is sized for that)
+			launchRadXFlux<ORDER>(lev, s, rad, cons_t, flux[0], 4, eps[0]);
+			launchRadMarchFlux<1, ORDER>(lev, s, rad, cons_t, flux[1], eps[1]);
 		} else {
-			launchRadXFlux<1>(lev, s, rad, cons_t, flux[0], 4, eps[0]);
+			launchRadFusedFlux<0, ORDER>(lev, s, rad, cons_t, flux[0], eps[0]);
 		}
-	} else {
-		QK_RAD_DIR(0)
-	}
-#undef QK_RAD_DIR
-#define QK_RAD_MARCH(D)                                                                                                                              \
-	if (order == 3) {                                                                                                                            \
-		launchRadMarchFlux<D, 3>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	} else if (order == 2) {                                                                                                                     \
-		launchRadMarchFlux<D, 2>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	} else {                                                                                                                                     \
-		launchRadMarchFlux<D, 1>(lev, s, rad, cons_t, flux[D], eps[D]);                                                                              \
-	}
-	if (ndim >= 2) {
-		QK_RAD_MARCH(1)
-	}
-	if (ndim == 3) {
-		QK_RAD_MARCH(2)
-	}
-#undef QK_RAD_MARCH
+		if (ndim == 3) {
+			launchRadMarchFlux<2, ORDER>(lev, s, rad, cons_t, flux[2], eps[2]);
+		}
+	});
 	return radStatus(lev, "computeRadiationFluxes");
 }
 
@@ -823,7 +734,7 @@ int qk_rad_PredictStep(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int 
 	const qk_array4 *f0 = fluxArray[0], *f1 = (ndim >= 2) ? fluxArray[1] : nullptr, *f2 = (ndim == 3) ? fluxArray[2] : nullptr;
 	const double dx0 = dx_in[0], dx1 = dx_in[1], dx2 = dx_in[2];
 	// (the build dimension is a compile-time constant of the kernel: with run-time branches the y and z flux loads of a cell wait for one another)
-	auto run = [&](auto ND) {
+	dispatchConst1to3(ndim, [&](auto ND) {
 	constexpr int NDIM = decltype(ND)::value;
 	launchRad(lev, s, 0, -1, "rad_PredictStep", [=] __device__(int b, int i, int j, int k, bool valid) {
 		if (!valid) {
@@ -835,7 +746,7 @@ int qk_rad_PredictStep(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int 
 		RA4 x2((NDIM >= 2) ? f1[b] : f0[b]); // (descriptors read once per cell, outside the component loops)
 		RA4 x3((NDIM == 3) ? f2[b] : f0[b]);
 		// one photon group: the state with the flux divergence added
-		auto update = [&](int pg, double cons[NRAD]) {
+		updateRadGroups(rad, Un, Un.idx(i, j, k), [&](int pg, double cons[NRAD]) {
 #pragma unroll
 			for (int n = 0; n < NRAD; ++n) {
 				double d = (dt / dx0) * (x1(i, j, k, pg + n) - x1(i + 1, j, k, pg + n));
@@ -847,40 +758,9 @@ int qk_rad_PredictStep(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int 
 				}
 				cons[n] = Uo(i, j, k, RAD0 + pg + n) + d;
 			}
-		};
-		// isStateValid is a property of the whole cell (radiation_system.hpp:626-644: every group), amendRadState then repairs every group
-		// (:646-665: a valid group below its floor is lifted as well).  Several groups: one pass for the verdict, one to store.
-		bool cellValid = true;
-		double cons[NRAD];
-		if (rad.ngroups > 1) {
-			for (int g = 0; g < rad.ngroups; ++g) {
-				update(NRAD * g, cons);
-				cellValid = cellValid && radStateValid(rad, cons);
-			}
-		}
-		for (int g = 0; g < rad.ngroups; ++g) {
-			const int pg = NRAD * g;
-			update(pg, cons);
-			if (rad.ngroups == 1) {
-				cellValid = radStateValid(rad, cons);
-			}
-			if (!cellValid) {
-				amendRadState(rad, cons);
-			}
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				Un(i, j, k, RAD0 + pg + n) = cons[n];
-			}
-		}
+		});
 	});
-	};
-	if (ndim == 3) {
-		run(std::integral_constant<int, 3>{});
-	} else if (ndim == 2) {
-		run(std::integral_constant<int, 2>{});
-	} else {
-		run(std::integral_constant<int, 1>{});
-	}
+	});
 	return radStatus(lev, "rad PredictStep");
 }
 
@@ -899,7 +779,7 @@ int qk_rad_AddFluxesRK2(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int
 	const qk_array4 *o0 = fluxArrayOld[0], *o1 = (ndim >= 2) ? fluxArrayOld[1] : nullptr, *o2 = (ndim == 3) ? fluxArrayOld[2] : nullptr;
 	const qk_array4 *f0 = fluxArray[0], *f1 = (ndim >= 2) ? fluxArray[1] : nullptr, *f2 = (ndim == 3) ? fluxArray[2] : nullptr;
 	const double dx0 = dx_in[0], dx1 = dx_in[1], dx2 = dx_in[2];
-	auto run = [&](auto ND) {
+	dispatchConst1to3(ndim, [&](auto ND) {
 	constexpr int NDIM = decltype(ND)::value;
 	launchRad(lev, s, 0, -1, "rad_AddFluxesRK2", [=] __device__(int b, int i, int j, int k, bool valid) {
 		if (!valid) {
@@ -915,7 +795,8 @@ int qk_rad_AddFluxesRK2(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int
 		// +-0 for finite fluxes and adding it can only change the sign of a zero result — they are not read (12 of the 36 words this kernel
 		// would otherwise stream).  Any other a32 takes the general form.
 		constexpr bool useOld = (0.5 - IMEX_a32) != 0.0;
-		auto update = [&](int pg, double cons[NRAD]) {
+		// (U_new may alias U1: updateRadGroups stores nothing before the whole-cell verdict)
+		updateRadGroups(rad, Un, Un.idx(i, j, k), [&](int pg, double cons[NRAD]) {
 #pragma unroll
 			for (int n = 0; n < NRAD; ++n) {
 				const double U_0 = U0(i, j, k, RAD0 + pg + n);
@@ -944,39 +825,9 @@ int qk_rad_AddFluxesRK2(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int
 				cons[n] = useOld ? (1.0 - IMEX_a32) * U_0 + IMEX_a32 * U_1 + ((0.5 - IMEX_a32) * (s0)) + (0.5 * (s1))
 						 : (1.0 - IMEX_a32) * U_0 + IMEX_a32 * U_1 + (0.5 * (s1));
 			}
-		};
-		// whole-cell validity, then every group repaired (see PredictStep); U_new may alias U1: nothing is stored before the verdict
-		bool cellValid = true;
-		double cons[NRAD];
-		if (rad.ngroups > 1) {
-			for (int g = 0; g < rad.ngroups; ++g) {
-				update(NRAD * g, cons);
-				cellValid = cellValid && radStateValid(rad, cons);
-			}
-		}
-		for (int g = 0; g < rad.ngroups; ++g) {
-			const int pg = NRAD * g;
-			update(pg, cons);
-			if (rad.ngroups == 1) {
-				cellValid = radStateValid(rad, cons);
-			}
-			if (!cellValid) {
-				amendRadState(rad, cons);
-			}
-#pragma unroll
-			for (int n = 0; n < NRAD; ++n) {
-				Un(i, j, k, RAD0 + pg + n) = cons[n];
-			}
-		}
+		});
 	});
-	};
-	if (ndim == 3) {
-		run(std::integral_constant<int, 3>{});
-	} else if (ndim == 2) {
-		run(std::integral_constant<int, 2>{});
-	} else {
-		run(std::integral_constant<int, 1>{});
-	}
+	});
 	return radStatus(lev, "rad AddFluxesRK2");
 }
 
@@ -1010,31 +861,17 @@ int qk_rad_stage_fused(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int 
 		a.eps[d] = (wavespeed_eps != nullptr) ? wavespeed_eps[d] : nullptr;
 	}
 	// the photon groups are transported independently (radiation_system.hpp:667-771 loops over them inside one kernel): one set of sweeps per group
-#define QK_RAD_SWEEPS(O)                                                                                                                             \
-	for (int g = 0; g < rad.ngroups; ++g) {                                                                                                      \
-	a.pg = NRAD * g;                                                                                                                             \
-	if (stage == 1) {                                                                                                                            \
-		if (store) {                                                                                                                         \
-			launchRadSweeps<O, 1, true>(lev, s, rad, a, 4);                                                                              \
-		} else {                                                                                                                             \
-			launchRadSweeps<O, 1, false>(lev, s, rad, a, 4);                                                                             \
-		}                                                                                                                                    \
-	} else {                                                                                                                                     \
-		if (store) {                                                                                                                         \
-			launchRadSweeps<O, 2, true>(lev, s, rad, a, 4);                                                                              \
-		} else {                                                                                                                             \
-			launchRadSweeps<O, 2, false>(lev, s, rad, a, 4);                                                                             \
-		}                                                                                                                                    \
-	}                                                                                                                                            \
-	}
-	if (order == 3) {
-		QK_RAD_SWEEPS(3)
-	} else if (order == 2) {
-		QK_RAD_SWEEPS(2)
-	} else {
-		QK_RAD_SWEEPS(1)
-	}
-#undef QK_RAD_SWEEPS
+	dispatchConst1to3(order, [&](auto O) {
+		constexpr int ORDER = decltype(O)::value;
+		for (int g = 0; g < rad.ngroups; ++g) {
+			a.pg = NRAD * g;
+			if (stage == 1) {
+				launchRadSweeps<ORDER, 1>(lev, s, rad, a, 4, store);
+			} else {
+				launchRadSweeps<ORDER, 2>(lev, s, rad, a, 4, store);
+			}
+		}
+	});
 	return radStatus(lev, "rad stage_fused");
 }
 

@@ -59,10 +59,12 @@ def test_shell_generators_match_oracle(ctx, oracle):
         assert np.allclose(so.rad_source(b, 0.0), sg.radEnergySource.fabs[b][0].cpu().numpy(), rtol=1e-13, atol=0.0)
 
 
-@pytest.mark.parametrize("mgs,rad_order", [(16, 2), (8, 2), (8, 3), (16, 1)])
-def test_radhydro_steps_bit_exact_with_shared_pow(ctx, oracle, mgs, rad_order):
-    """(rad_order: the problem uses PLM = 2; 3 and 1 exercise the PPM and donor-cell variants of the three flux kernels in 3-D)"""
-    N, nsteps = 16, 3
+@pytest.mark.parametrize("N,mgs,rad_order", [pytest.param(16, 16, 2, id="16-2"), pytest.param(16, 8, 2, id="8-2"), pytest.param(16, 8, 3, id="8-3"),
+                                             pytest.param(16, 16, 1, id="16-1"), (20, 20, 3), (20, 20, 2)])  # (the 16^3 cases keep their ids)
+def test_radhydro_steps_bit_exact_with_shared_pow(ctx, oracle, N, mgs, rad_order):
+    """(rad_order: the problem uses PLM = 2; 3 and 1 exercise the PPM and donor-cell variants of the three flux kernels in 3-D.
+    The single 20^3 box: a Y strip of 16 cells and a tail of 4, marches of 8 + 8 + 5 faces, an X slab of 560 positions in three workgroups)"""
+    nsteps = 3
     so, sg = make_pair(ctx, oracle, N, mgs, 1)
     so.set_rad_reconstruction_order(rad_order)
     sg.radiationReconstructionOrder_ = rad_order
@@ -339,11 +341,14 @@ def test_fused_radiation_stage_equals_the_separate_operators(ctx, rad_order):
     """qk_rad_stage_fused (three sweeps that take the flux divergence where the fluxes are produced; the Z sweep finishes PredictStep /
     AddFluxesRK2 and writes the stage-2 state in place) against computeRadiationFluxes + PredictStep / AddFluxesRK2: every component of the
     state and, when they are asked for (flux registers), the face fluxes of both stages, bit for bit.  The shell at 16^3 in 8^3 boxes and in a
-    single 16^3 box (the Y sweep marches strips of 16 cells; tests/test_full_size_configs_gpu.py runs 128^3 boxes: eight strips per pencil)."""
-    for mgs in (8, 16):
+    single 16^3 box (the Y sweep marches strips of 16 cells; tests/test_full_size_configs_gpu.py runs 128^3 boxes: eight strips per pencil), and
+    in a single 40^3 box, the smallest with strip seams and tail strips everywhere: Y strips of 16 + 16 + 8 cells, Z strips of 32 + 8 (stage 1; stage 2
+    marches whole pencils), 41 flux faces = 5 strips of 8 + one that holds only the last face, 48 x 40 = 1920 slab positions per plane in eight X
+    workgroups whose seams fall in mid-row, a partial wave of 40 lanes along x."""
+    for N, mgs in ((16, 8), (16, 16), (40, 40)):
         sims = []
         for fused in (True, False):
-            s = shell_problem(ctx, 16, table(), max_grid_size=mgs, pow_mode=1)
+            s = shell_problem(ctx, N, table(), max_grid_size=mgs, pow_mode=1)
             s.radiationReconstructionOrder_ = rad_order
             assert s.use_fused_rad
             s.use_fused_rad = fused
@@ -357,7 +362,7 @@ def test_fused_radiation_stage_equals_the_separate_operators(ctx, rad_order):
         for d in range(3):
             for fa, fb in ((a.radFluxOld[d], b.radFluxOld[d]), (a.radFlux[d], b.radFlux[d])):
                 for n in range(a.lev.nboxes):
-                    assert torch.equal(fa.fabs[n], fb.fabs[n]), (mgs, d, n)
+                    assert torch.equal(fa.fabs[n], fb.fabs[n]), (N, mgs, d, n)
         assert a.rad_counters == b.rad_counters
 
 
