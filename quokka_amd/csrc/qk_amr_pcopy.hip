@@ -223,16 +223,40 @@ int qk_pcopy_plan_create(qk_ctx *ctx, const qk_geometry *geom, int n_src, const 
 			dst_local[g] = P->ndst_local++;
 		}
 	}
+	// periodic shifts: a destination cell and the source cell it is an image of lie as many periods apart as the two grown layouts reach past
+	// each other — one period for boxes inside the domain with ghost widths up to the domain width, more where a periodic direction is narrower
+	// than src_nghost + dst_nghost (or a box straddles a periodic face); ascending, so that the canonical order is the one of -1, 0, +1 wherever
+	// one period suffices
 	std::vector<std::array<int, 3>> shifts;
 	int rng[3] = {0, 0, 0};
+	int width[3] = {1, 1, 1};
+	for (int d = 0; d < 3; ++d) {
+		width[d] = geom->domain.hi[d] - geom->domain.lo[d] + 1;
+	}
 	for (int d = 0; d < ndim; ++d) {
-		rng[d] = (geom->periodic[d] != 0) ? 1 : 0;
+		QK_REQUIRE(ctx, width[d] >= 1, "qk_pcopy_plan_create: empty domain");
+		if (geom->periodic[d] == 0) {
+			continue;
+		}
+		rng[d] = 1;
+		if (n_src > 0 && n_dst > 0) {
+			int slo = src_boxes[0].lo[d], shi = src_boxes[0].hi[d], dlo = dst_boxes[0].lo[d], dhi = dst_boxes[0].hi[d];
+			for (int g = 0; g < n_src; ++g) {
+				slo = std::min(slo, src_boxes[g].lo[d]);
+				shi = std::max(shi, src_boxes[g].hi[d]);
+			}
+			for (int g = 0; g < n_dst; ++g) {
+				dlo = std::min(dlo, dst_boxes[g].lo[d]);
+				dhi = std::max(dhi, dst_boxes[g].hi[d]);
+			}
+			const int reach = std::max(dhi - slo, shi - dlo) + src_nghost + dst_nghost; // largest |destination index - source index|
+			rng[d] = std::max(1, reach / width[d]);
+		}
 	}
 	for (int sz = -rng[2]; sz <= rng[2]; ++sz) {
 		for (int sy = -rng[1]; sy <= rng[1]; ++sy) {
 			for (int sx = -rng[0]; sx <= rng[0]; ++sx) {
-				shifts.push_back({sx * (geom->domain.hi[0] - geom->domain.lo[0] + 1), sy * (geom->domain.hi[1] - geom->domain.lo[1] + 1),
-						  sz * (geom->domain.hi[2] - geom->domain.lo[2] + 1)});
+				shifts.push_back({sx * width[0], sy * width[1], sz * width[2]});
 			}
 		}
 	}

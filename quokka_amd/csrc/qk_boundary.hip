@@ -268,6 +268,15 @@ inline auto gridFor(int64_t cells, int nitems) -> dim3
 	const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((cells + 255) / 256, 256));
 	return dim3(static_cast<unsigned>(gx), static_cast<unsigned>(nitems), 1);
 }
+constexpr int MAX_ITEMS_PER_LAUNCH = 65535; // (the items of a launch live in gridDim.y)
+
+// one launch per run of at most 65535 items of [0, count): launch(first, n)  (as forItemChunks of qk_amr_pcopy.hip)
+template <class Launch> void forItemChunks(int count, Launch &&launch)
+{
+	for (int a = 0; a < count; a += MAX_ITEMS_PER_LAUNCH) {
+		launch(a, std::min(count - a, MAX_ITEMS_PER_LAUNCH));
+	}
+}
 
 } // namespace
 
@@ -303,17 +312,23 @@ int qk_ghost_plan_create(qk_level *lev, qk_ghost_plan **plan_out, const qk_geome
 	P->nghost = nghost;
 	P->ncomp = ncomp;
 
-	// periodic shifts
+	// periodic shifts: a ghost cell lies up to nghost cells beyond a periodic face, i.e. ceil(nghost / domain width) periods away from the valid cell
+	// it is an image of (more than one where a periodic direction is narrower than the ghost width); ascending, so that the canonical order
+	// of the items is the one of the shifts -1, 0, +1 wherever one period suffices
 	std::vector<std::array<int, 3>> shifts;
 	int rng[3] = {0, 0, 0};
+	int width[3] = {1, 1, 1};
+	for (int d = 0; d < 3; ++d) {
+		width[d] = geom->domain.hi[d] - geom->domain.lo[d] + 1;
+	}
 	for (int d = 0; d < geom->ndim; ++d) {
-		rng[d] = (geom->periodic[d] != 0) ? 1 : 0;
+		QK_REQUIRE(ctx, width[d] >= 1, "qk_ghost_plan_create: empty domain");
+		rng[d] = (geom->periodic[d] != 0) ? std::max(1, (nghost + width[d] - 1) / width[d]) : 0;
 	}
 	for (int sz = -rng[2]; sz <= rng[2]; ++sz) {
 		for (int sy = -rng[1]; sy <= rng[1]; ++sy) {
 			for (int sx = -rng[0]; sx <= rng[0]; ++sx) {
-				shifts.push_back({sx * (geom->domain.hi[0] - geom->domain.lo[0] + 1), sy * (geom->domain.hi[1] - geom->domain.lo[1] + 1),
-						  sz * (geom->domain.hi[2] - geom->domain.lo[2] + 1)});
+				shifts.push_back({sx * width[0], sy * width[1], sz * width[2]});
 			}
 		}
 	}
@@ -546,8 +561,10 @@ int qk_FillBoundary_local(qk_ghost_plan *plan, qk_stream s, qk_array4 *state_t)
 	}
 	const int nc = (plan->active_ncomp < 0) ? plan->ncomp : plan->active_ncomp;
 	ProfScope ps(ctx, static_cast<hipStream_t>(s), "ghost_copy_local");
-	hipLaunchKernelGGL(k_copy<MODE_LOCAL>, gridFor(static_cast<int64_t>(plan->max_local_cells) * nc, static_cast<int>(plan->local.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), plan->d_local, state_t, static_cast<double *>(nullptr), nc, plan->active_scomp);
+	forItemChunks(static_cast<int>(plan->local.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_LOCAL>, gridFor(static_cast<int64_t>(plan->max_local_cells) * nc, n), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_local + first,
+				   state_t, static_cast<double *>(nullptr), nc, plan->active_scomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -563,9 +580,10 @@ int qk_FillBoundary_local_int(qk_ghost_plan *plan, qk_stream s, qk_iarray4 *stat
 	if (plan->local.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL((k_copy<MODE_LOCAL, int, qk_iarray4>),
-			   gridFor(static_cast<int64_t>(plan->max_local_cells) * plan->ncomp, static_cast<int>(plan->local.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), plan->d_local, state_t, static_cast<int *>(nullptr), plan->ncomp);
+	forItemChunks(static_cast<int>(plan->local.size()), [&](int first, int n) {
+		hipLaunchKernelGGL((k_copy<MODE_LOCAL, int, qk_iarray4>), gridFor(static_cast<int64_t>(plan->max_local_cells) * plan->ncomp, n), dim3(256), 0,
+				   static_cast<hipStream_t>(s), plan->d_local + first, state_t, static_cast<int *>(nullptr), plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -581,8 +599,10 @@ int qk_SumBoundary_local(qk_ghost_plan *plan, qk_stream s, qk_array4 *state_t)
 	if (plan->local.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_copy<MODE_SUM_LOCAL>, gridFor(static_cast<int64_t>(plan->max_local_cells) * plan->ncomp, static_cast<int>(plan->local.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), plan->d_local, state_t, static_cast<double *>(nullptr), plan->ncomp);
+	forItemChunks(static_cast<int>(plan->local.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_SUM_LOCAL>, gridFor(static_cast<int64_t>(plan->max_local_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_local + first,
+				   state_t, static_cast<double *>(nullptr), plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -598,8 +618,10 @@ int qk_SumBoundary_pack(qk_ghost_plan *plan, qk_stream s, int k, const qk_array4
 	if (pp.recv.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_copy<MODE_SUM_PACK>, gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, static_cast<int>(pp.recv.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), pp.d_recv, const_cast<qk_array4 *>(state_t), buf, plan->ncomp);
+	forItemChunks(static_cast<int>(pp.recv.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_SUM_PACK>, gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_recv + first,
+				   const_cast<qk_array4 *>(state_t), buf, plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -615,8 +637,10 @@ int qk_SumBoundary_unpack(qk_ghost_plan *plan, qk_stream s, int k, qk_array4 *st
 	if (pp.send.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_copy<MODE_SUM_UNPACK>, gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, static_cast<int>(pp.send.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), pp.d_send, state_t, const_cast<double *>(buf), plan->ncomp);
+	forItemChunks(static_cast<int>(pp.send.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_SUM_UNPACK>, gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_send + first,
+				   state_t, const_cast<double *>(buf), plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -632,8 +656,10 @@ int qk_FillBoundary_pack_int(qk_ghost_plan *plan, qk_stream s, int k, const qk_i
 	if (pp.send.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL((k_copy<MODE_PACK, int, qk_iarray4>), gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, static_cast<int>(pp.send.size())),
-			   dim3(256), 0, static_cast<hipStream_t>(s), pp.d_send, const_cast<qk_iarray4 *>(state_t), sendbuf, plan->ncomp);
+	forItemChunks(static_cast<int>(pp.send.size()), [&](int first, int n) {
+		hipLaunchKernelGGL((k_copy<MODE_PACK, int, qk_iarray4>), gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_send + first,
+				   const_cast<qk_iarray4 *>(state_t), sendbuf, plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -649,8 +675,10 @@ int qk_FillBoundary_unpack_int(qk_ghost_plan *plan, qk_stream s, int k, qk_iarra
 	if (pp.recv.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL((k_copy<MODE_UNPACK, int, qk_iarray4>), gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, static_cast<int>(pp.recv.size())),
-			   dim3(256), 0, static_cast<hipStream_t>(s), pp.d_recv, state_t, const_cast<int *>(recvbuf), plan->ncomp);
+	forItemChunks(static_cast<int>(pp.recv.size()), [&](int first, int n) {
+		hipLaunchKernelGGL((k_copy<MODE_UNPACK, int, qk_iarray4>), gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_recv + first,
+				   state_t, const_cast<int *>(recvbuf), plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -666,8 +694,10 @@ int qk_FillBoundary_pack(qk_ghost_plan *plan, qk_stream s, int k, const qk_array
 	if (pp.send.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_copy<MODE_PACK>, gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, static_cast<int>(pp.send.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), pp.d_send, const_cast<qk_array4 *>(state_t), sendbuf, plan->ncomp);
+	forItemChunks(static_cast<int>(pp.send.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_PACK>, gridFor(static_cast<int64_t>(pp.max_send_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_send + first,
+				   const_cast<qk_array4 *>(state_t), sendbuf, plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -683,8 +713,10 @@ int qk_FillBoundary_unpack(qk_ghost_plan *plan, qk_stream s, int k, qk_array4 *s
 	if (pp.recv.empty()) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_copy<MODE_UNPACK>, gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, static_cast<int>(pp.recv.size())), dim3(256), 0,
-			   static_cast<hipStream_t>(s), pp.d_recv, state_t, const_cast<double *>(recvbuf), plan->ncomp);
+	forItemChunks(static_cast<int>(pp.recv.size()), [&](int first, int n) {
+		hipLaunchKernelGGL(k_copy<MODE_UNPACK>, gridFor(static_cast<int64_t>(pp.max_recv_cells) * plan->ncomp, n), dim3(256), 0, static_cast<hipStream_t>(s), pp.d_recv + first,
+				   state_t, const_cast<double *>(recvbuf), plan->ncomp);
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
@@ -788,15 +820,16 @@ int qk_FillPhysicalBoundary_subset(qk_ghost_plan *plan, qk_stream s, qk_array4 *
 		plan->h_physbc.assign(reinterpret_cast<const unsigned char *>(&pa), reinterpret_cast<const unsigned char *>(&pa) + sizeof(PhysBcArgs));
 	}
 	ProfScope ps(ctx, static_cast<hipStream_t>(s), "ghost_physbc");
-	if (pa.has_dirichlet != 0) {
-		hipLaunchKernelGGL(k_physbc<true>, gridFor(plan->max_shell_cells, count), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_shells + first, state_t,
-				   plan->geom, (plan->active_ncomp < 0) ? plan->ncomp : plan->active_ncomp, static_cast<const PhysBcArgs *>(plan->d_physbc),
-				   plan->active_scomp);
-	} else {
-		hipLaunchKernelGGL(k_physbc<false>, gridFor(plan->max_shell_cells, count), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_shells + first, state_t,
-				   plan->geom, (plan->active_ncomp < 0) ? plan->ncomp : plan->active_ncomp, static_cast<const PhysBcArgs *>(plan->d_physbc),
-				   plan->active_scomp);
-	}
+	const int nc = (plan->active_ncomp < 0) ? plan->ncomp : plan->active_ncomp;
+	forItemChunks(count, [&](int a, int n) {
+		if (pa.has_dirichlet != 0) {
+			hipLaunchKernelGGL(k_physbc<true>, gridFor(plan->max_shell_cells, n), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_shells + first + a, state_t,
+					   plan->geom, nc, static_cast<const PhysBcArgs *>(plan->d_physbc), plan->active_scomp);
+		} else {
+			hipLaunchKernelGGL(k_physbc<false>, gridFor(plan->max_shell_cells, n), dim3(256), 0, static_cast<hipStream_t>(s), plan->d_shells + first + a, state_t,
+					   plan->geom, nc, static_cast<const PhysBcArgs *>(plan->d_physbc), plan->active_scomp);
+		}
+	});
 	QK_HIP_CHECK(ctx, hipGetLastError());
 	return QK_OK;
 }
