@@ -652,6 +652,42 @@ enum { QK_COOLING_TGAS_FROM_EGAS = 0, QK_COOLING_EGAS_FROM_TGAS = 1, QK_COOLING_
 int qk_cooling_evaluate(qk_ctx *ctx, qk_stream s, const qk_cloudy_tables *device_tables, double gamma, int what, int64_t n, const double *d_rho, const double *d_value,
 			double *d_out);
 
+/* ------------------------------------------------------------------ tracer particles (one level, one rank; qk_tracer.hip)
+ * Particles are structure-of-arrays in device memory owned by the caller: pos[d] / vel[d] (double; vel is the reference's rdata), d < ndim (the other
+ * pointers are not read and may be NULL), id (int64), cpu (int32).
+ * The plan maps a global cell index to its box in O(1): a dense lattice of box indices at the granularity of the common divisor of all box edges, for
+ * any BoxArray that tiles the domain (remainder boxes included).  It also holds prob_lo, prob_hi, dx, 1 / dx, n_cell and the periodicity.  A level
+ * whose boxes do not tile the domain exactly once (a refined level, several ranks), or a direction with 32768 cells or more: QK_ERR_UNSUPPORTED. */
+typedef struct qk_tracer_plan qk_tracer_plan;
+int qk_tracer_plan_create(qk_level *lev, qk_tracer_plan **plan, const qk_geometry *geom, const double prob_lo[3], const double prob_hi[3], const double dx[3]);
+int qk_tracer_plan_destroy(qk_tracer_plan *plan);
+/* Introspection only (host; no counterpart in the reference, no kernel reads it): the lattice granularity per direction and the number of lattice
+ * entries.  The tests read it to assert which advection kernel ran (lattice in LDS or in global memory) and the granularity a remainder box gives. */
+int qk_tracer_plan_lattice(qk_tracer_plan *plan, int granularity[3], int64_t *nentries);
+/* InitOnePerCell: one particle per valid cell at prob_lo + (i + off) * dx, vel = 0, cpu = rank     reference src/simulation.hpp:1993-2005 (off = 0.5)
+ * Ids run from first_id over the level's boxes in box order, cells in Fortran order (i fastest) — this project's numbering: AMReX's is not pinned.
+ * The arrays hold one entry per valid cell of the level. */
+int qk_tracer_InitOnePerCell(qk_tracer_plan *plan, qk_stream s, const double off[3], double *const pos[3], double *const vel[3], int64_t *id, int *cpu,
+			     int64_t first_id, int rank);
+/* TracerParticleContainer::AdvectWithUmac(umac, lev, dt), both passes of the predictor-corrector in one kernel
+ *                                                                     reference src/QuokkaSimulation.hpp:1290-1314 (call), :1061-1073 (umac)
+ * umac[d], d < ndim: face-centred table (facedir = d, 1 component, NO ghost faces).  Per particle, with I the MAC interpolation below:
+ *   v0 = I(x);  xm = x + (0.5 dt) v0;  v1 = I(xm);  x <- x + dt v1;  vel <- v1.
+ * I_d(x): for e < ndim  l_e = (x_e - plo_e) * dxi_e, minus 0.5 if e != d;  i_e = floor(l_e), w_e = l_e - i_e, s_e = {1 - w_e, w_e};
+ *   I_d = sum_kk sum_jj sum_ii ((s_0[ii] * s_1[jj]) * s_2[kk]) * u_d(i_0 + ii, i_1 + jj, i_2 + kk), accumulated from 0.0, kk outermost, ii innermost
+ *   (2-D: no kk loop, no s_2; 1-D: s_0 alone).
+ * An index outside the domain is wrapped modulo n_cell in a periodic direction (face N == face 0) and clamped otherwise (cells to [0, N - 1], faces of
+ * the normal direction to [0, N]): what the reference's two ghost faces hold (int_dir / foextrap, src/simulation.hpp:182-205).  A face shared by two
+ * boxes is read from the box whose low face it is, the domain's top face from the last box. */
+int qk_tracer_AdvectWithUmac(qk_tracer_plan *plan, qk_stream s, const qk_array4 *const umac[3], double dt, int64_t np, double *const pos[3],
+			     double *const vel[3]);
+/* Redistribute on one level and one rank (ngrow = 0)                                                reference src/simulation.hpp:1317-1329
+ * Periodic direction, x outside [plo, phi): x -= floor((x - plo) / (phi - plo)) * (phi - plo) — one period outside: exactly x -+ (phi - plo); any number
+ * of periods is shifted back — and a result below plo or on phi through rounding becomes plo.
+ * keep[n] (one byte per particle) = 1 if the particle then lies in [plo, phi) in every direction, else 0 (AMReX invalidates a particle that left
+ * through a non-periodic face; a NaN or infinite position is dropped as well).  Compacting the arrays by `keep` is the caller's. */
+int qk_tracer_Redistribute(qk_tracer_plan *plan, qk_stream s, int64_t np, double *const pos[3], unsigned char *keep);
+
 #ifdef __cplusplus
 }
 #endif

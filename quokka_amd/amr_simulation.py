@@ -665,6 +665,7 @@ class AmrSimulation:
         self.ErrorEst: Optional[Callable[["AmrSimulation", int, MultiFab], None]] = None  # (amr, lev, tags) -> sets tags on level lev
         self.initial_conditions: Optional[Callable] = None  # fn(geom_of_level) -> fn(i, j, k) -> conserved state on index grids
         self.static_fine_boxes: Optional[List[List[Box]]] = None  # [lev-1] -> boxes of level lev: fixed grids instead of ErrorEst
+        self.do_tracers = 0  # (reference src/simulation.hpp:398) tracer particles live on one unrefined level (quokka_amd/tracers.py): refused here
 
     @property
     def finest_level(self) -> int:
@@ -1118,6 +1119,8 @@ class AmrSimulation:
                 L._new_ghosts_filled = False
 
     def step(self):
+        if self.do_tracers:
+            raise capi.QkError("do_tracers: tracer particles are not built for the AMR driver (no Redistribute between levels); use HydroSimulation")
         self.computeTimestep()
         self.timeStepWithSubcycling(0, self.tNew_)
         self.tNew_ += self.dt_[0]

@@ -242,6 +242,13 @@ def lib() -> C.CDLL:
         L.qk_ParallelCopy_local.argtypes = [vp, vp, vp, vp, ci, ci, ci]
         L.qk_ParallelCopy_pack.argtypes = [vp, vp, ci, vp, ci, vp]
         L.qk_ParallelCopy_unpack.argtypes = [vp, vp, ci, vp, ci, vp, ci]
+    # tracer particles (csrc/qk_tracer.hip): no hasattr guard — a library without them is an error, not a reason to run without
+    L.qk_tracer_plan_create.argtypes = [vp, P(vp), P(Geometry), cd * 3, cd * 3, cd * 3]
+    L.qk_tracer_plan_destroy.argtypes = [vp]
+    L.qk_tracer_plan_lattice.argtypes = [vp, ci * 3, P(C.c_int64)]
+    L.qk_tracer_InitOnePerCell.argtypes = [vp, vp, cd * 3, vp * 3, vp * 3, vp, vp, C.c_int64, ci]
+    L.qk_tracer_AdvectWithUmac.argtypes = [vp, vp, vp * 3, cd, C.c_int64, vp * 3, vp * 3]
+    L.qk_tracer_Redistribute.argtypes = [vp, vp, C.c_int64, vp * 3, vp]
     _lib = L
     return L
 
@@ -271,6 +278,7 @@ DECLARED_SYMBOLS = [
     "qk_cloudy_tables_read", "qk_cloudy_tables_free", "qk_cooling_tabulated", "qk_cooling_evaluate",
     "qk_fluxreg_create_crse_part", "qk_pcopy_plan_create", "qk_pcopy_plan_destroy", "qk_pcopy_plan_num_peers", "qk_pcopy_plan_peer", "qk_pcopy_plan_num_items",
     "qk_pcopy_plan_item", "qk_ParallelCopy_local", "qk_ParallelCopy_pack", "qk_ParallelCopy_unpack",
+    "qk_tracer_plan_create", "qk_tracer_plan_destroy", "qk_tracer_plan_lattice", "qk_tracer_InitOnePerCell", "qk_tracer_AdvectWithUmac", "qk_tracer_Redistribute",
 ]
 
 

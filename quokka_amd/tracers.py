@@ -1,0 +1,131 @@
+"""Tracer particles of one level on one rank (reference src/simulation.hpp:398, :593, :1993-2005, :1317-1329; src/QuokkaSimulation.hpp:1290-1314):
+one particle per cell, advected with the time-averaged face velocity of the RK2 step.
+
+Host plumbing only: the particle arrays are torch tensors (structure of arrays, as the C-ABI takes them), every particle is moved by the HIP kernels
+of csrc/qk_tracer.hip.  Compaction after a Redistribute that dropped particles is a boolean mask over the arrays, order-preserving.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Sequence
+
+import numpy as np
+import torch
+
+from . import capi
+from .multifab import MultiFab
+
+
+def _d3(v: Sequence[float]):
+    return (C.c_double * 3)(*[float(x) for x in (list(v) + [0.0, 0.0, 0.0])[:3]])
+
+
+class TracerParticles:
+    """amrex::TracerParticleContainer for a HydroSimulation: pos / vel (double, per direction), id (int64), cpu (int32) in device memory."""
+
+    def __init__(self, sim):
+        self.sim, self.ctx, self.lev, self.geom = sim, sim.ctx, sim.lev, sim.geom
+        self.ndim = sim.geom.ndim
+        g = sim.geom
+        self._geom_c = g.c_struct()
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.qk_tracer_plan_create(self.lev.h, C.byref(h), C.byref(self._geom_c), _d3(g.prob_lo), _d3(g.prob_hi), _d3(g.dx)),
+                       "qk_tracer_plan_create")
+        self.h = h
+        self.last_keep = None
+        self._alloc(0)
+
+    def _alloc(self, n: int):
+        dev = self.ctx.device
+        self.pos: List[torch.Tensor] = [torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(self.ndim)]
+        self.vel: List[torch.Tensor] = [torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(self.ndim)]
+        self.id = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.cpu = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    @staticmethod
+    def _ptrs(arrs: Sequence[torch.Tensor]):
+        return (C.c_void_p * 3)(*[C.c_void_p(a.data_ptr()) if a.numel() > 0 else None for a in arrs] + [None] * (3 - len(arrs)))
+
+    @property
+    def num_particles(self) -> int:
+        return int(self.id.numel())
+
+    def lattice(self):
+        """(granularity per direction, number of entries) of the plan's cell -> box lattice"""
+        gran, n = (C.c_int * 3)(), C.c_int64()
+        self.ctx.check(self.ctx.L.qk_tracer_plan_lattice(self.h, gran, C.byref(n)), "qk_tracer_plan_lattice")
+        return list(gran), int(n.value)
+
+    # ------------------------------------------------------------------ the three operations
+    def init_one_per_cell(self, off: Sequence[float] = (0.5, 0.5, 0.5), first_id: int = 1):
+        """InitOnePerCell(0.5, 0.5, 0.5, pdata) (reference src/simulation.hpp:1993-2005).  Ids run from `first_id` over the boxes in order, cells
+        in Fortran order: this project's numbering."""
+        self._alloc(self.lev.num_cells())
+        if self.num_particles == 0:
+            return
+        c = self.ctx
+        c.check(c.L.qk_tracer_InitOnePerCell(self.h, c.stream(), _d3(off), self._ptrs(self.pos), self._ptrs(self.vel), C.c_void_p(self.id.data_ptr()),
+                                            C.c_void_p(self.cpu.data_ptr()), int(first_id), int(self.sim.rank)), "qk_tracer_InitOnePerCell")
+
+    def advect(self, umac: Sequence[MultiFab], dt: float):
+        """AdvectWithUmac(umac, lev, dt): umac[d] face-centred in d, one component, no ghost faces"""
+        assert len(umac) >= self.ndim
+        for d in range(self.ndim):
+            assert umac[d].facedir == d and umac[d].ncomp == 1 and umac[d].nghost == 0 and umac[d].level is self.lev
+        if self.num_particles == 0:
+            return
+        c = self.ctx
+        tabs = (C.c_void_p * 3)(*[umac[d].ptr if d < self.ndim else None for d in range(3)])
+        c.check(c.L.qk_tracer_AdvectWithUmac(self.h, c.stream(), tabs, float(dt), self.num_particles, self._ptrs(self.pos), self._ptrs(self.vel)),
+                "qk_tracer_AdvectWithUmac")
+
+    def redistribute(self) -> int:
+        """Redistribute(lev, lev, ngrow = 0): periodic shift, particles beyond a non-periodic face dropped.  Returns the number dropped."""
+        n = self.num_particles
+        c = self.ctx
+        keep = self.last_keep = torch.empty(n, dtype=torch.bool, device=c.device)  # (kept: which particles of the last call stayed)
+        if n == 0:
+            return 0
+        c.check(c.L.qk_tracer_Redistribute(self.h, c.stream(), n, self._ptrs(self.pos), C.c_void_p(keep.data_ptr())), "qk_tracer_Redistribute")
+        if bool(keep.all()):  # (one device -> host read per step)
+            return 0
+        self.pos = [a[keep] for a in self.pos]
+        self.vel = [a[keep] for a in self.vel]
+        self.id, self.cpu = self.id[keep], self.cpu[keep]
+        return n - self.num_particles
+
+    # ------------------------------------------------------------------ retries, save and restore
+    def snapshot(self) -> Dict[str, object]:
+        return {"pos": [a.clone() for a in self.pos], "vel": [a.clone() for a in self.vel], "id": self.id.clone(), "cpu": self.cpu.clone()}
+
+    def restore(self, snap: Dict[str, object]):
+        """back to a snapshot(); the snapshot stays usable for further retries"""
+        self.pos = [a.clone() for a in snap["pos"]]
+        self.vel = [a.clone() for a in snap["vel"]]
+        self.id, self.cpu = snap["id"].clone(), snap["cpu"].clone()
+
+    def positions(self) -> np.ndarray:
+        return torch.stack(self.pos, dim=1).cpu().numpy() if self.num_particles else np.zeros((0, self.ndim))
+
+    def velocities(self) -> np.ndarray:
+        return torch.stack(self.vel, dim=1).cpu().numpy() if self.num_particles else np.zeros((0, self.ndim))
+
+    def ids(self) -> np.ndarray:
+        return self.id.cpu().numpy()
+
+    def load(self, positions, velocities, ids):
+        """take over the particles of a saved run: positions / velocities (np, ndim), ids (np,); cpu = this rank"""
+        p, v, i = np.asarray(positions, dtype=np.float64), np.asarray(velocities, dtype=np.float64), np.asarray(ids, dtype=np.int64)
+        if p.ndim != 2 or p.shape[1] != self.ndim or v.shape != p.shape or i.shape != (p.shape[0],):
+            raise capi.QkError(f"TracerParticles.load: expected positions and velocities of shape (np, {self.ndim}) and ids of shape (np,)")
+        dev = self.ctx.device
+        self.pos = [torch.from_numpy(np.ascontiguousarray(p[:, d])).to(dev) for d in range(self.ndim)]
+        self.vel = [torch.from_numpy(np.ascontiguousarray(v[:, d])).to(dev) for d in range(self.ndim)]
+        self.id = torch.from_numpy(np.ascontiguousarray(i)).to(dev)
+        self.cpu = torch.full((p.shape[0],), int(self.sim.rank), dtype=torch.int32, device=dev)
+
+    def __del__(self):
+        try:
+            self.ctx.L.qk_tracer_plan_destroy(self.h)
+        except Exception:
+            pass
