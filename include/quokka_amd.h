@@ -652,6 +652,13 @@ enum { QK_COOLING_TGAS_FROM_EGAS = 0, QK_COOLING_EGAS_FROM_TGAS = 1, QK_COOLING_
 int qk_cooling_evaluate(qk_ctx *ctx, qk_stream s, const qk_cloudy_tables *device_tables, double gamma, int what, int64_t n, const double *d_rho, const double *d_value,
 			double *d_out);
 
+/* ------------------------------------------------------------------ arithmetic primitives (introspection for tests)
+ * The hand-rolled FP64 division and square root of csrc/qk_device.hpp, which every kernel's "same bits as `/` and sqrt" rests on, over n elements in
+ * device memory: out[i] = divBy(a[i], recipOf(b[i])), divN(a[i], b[i]), recipExact(b[i]) (d_a not read, may be NULL) or sqrtN(a[i]) (d_b not read,
+ * may be NULL).  The kernel calls the functions of qk_device.hpp; it holds no copy of them. */
+enum { QK_ARITH_DIVBY_RECIPOF = 0, QK_ARITH_DIVN = 1, QK_ARITH_RECIPEXACT = 2, QK_ARITH_SQRTN = 3 };
+int qk_arith_evaluate(qk_ctx *ctx, qk_stream s, int what, int64_t n, const double *d_a, const double *d_b, double *d_out);
+
 /* ------------------------------------------------------------------ tracer particles (one level, one rank; qk_tracer.hip)
  * Particles are structure-of-arrays in device memory owned by the caller: pos[d] / vel[d] (double; vel is the reference's rdata), d < ndim (the other
  * pointers are not read and may be NULL), id (int64), cpu (int32).

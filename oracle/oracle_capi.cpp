@@ -615,4 +615,103 @@ void orc_cloudy_compute_cooling(void *p, double gamma, double dt, double T_floor
 	}
 }
 
+// ------------------------------------------------------------------ the matter-radiation exchange, cell by cell
+// The radiation and EOS traits of one single-group problem as a closed set: the fields of qk_rad_traits / qk_hydro_traits (include/quokka_amd.h)
+// the exchange reads.  gamma == 1: isothermal.
+struct orc_rad_cell_traits {
+	double c_light, c_hat, radiation_constant, Erad_floor;
+	double kappaP, kappaE, kappaF;
+	double opacity_T_ref, opacity_T_exponent, opacity_pow_floor;
+	double gamma, mean_molecular_weight, boltzmann_constant;
+	int beta_order, opacity_model, pow_mode, eddington_model;
+};
+
+// the three opacity hooks as the closed set of qk_rad_traits::opacity_model (0: constant, 1: k0 / rho, 2: k0 max((T / T_ref)^p, floor) / rho);
+// pow_mode 1: the exponents 3, -3 and -3.5 as products and square roots, as in setupMarshakAsymptotic / setupRadPulse (problems.hpp)
+static auto closedOpacity(orc_rad_cell_traits const &t, double k0) -> std::function<double(double, double)>
+{
+	if (t.opacity_model == 0) {
+		return [k0](double, double) { return k0; };
+	}
+	if (t.opacity_model == 1) {
+		return [k0](double rho, double) { return k0 / rho; };
+	}
+	const double T_ref = t.opacity_T_ref, p = t.opacity_T_exponent, floor = t.opacity_pow_floor;
+	const int pow_mode = t.pow_mode;
+	return [=](double rho, double T) {
+		const double x = T / T_ref;
+		double pw = NAN;
+		if (pow_mode == 1 && p == 3.0) {
+			pw = (x * x) * x;
+		} else if (pow_mode == 1 && p == -3.0) {
+			pw = 1.0 / ((x * x) * x);
+		} else if (pow_mode == 1 && p == -3.5) {
+			pw = 1.0 / (((x * x) * x) * std::sqrt(x));
+		} else {
+			pw = std::pow(x, p);
+		}
+		return (k0 * ((pw > floor) ? pw : floor)) / rho;
+	};
+}
+
+// AddSourceTermsSingleGroup on each of n cells as a box of its own.  U[10][n] (component outermost) is updated in place, src[n] is the radiation
+// energy source.  per_cell[5][n]: solves, Newton iterations summed over the solves (n + 1 per solve, the counter's convention), the largest
+// n + 1 of one solve, Newton failures, outer-iteration failures.  totals[7]: p_iteration_counter[0..3] then p_iteration_failure_counter[0..2].
+void orc_rad_source_cells(orc_rad_cell_traits const *t, long n, double *U, double const *src, double dt_radiation, int stage, int *per_cell, long *totals)
+{
+	RadSystem rs;
+	rs.rt.c_light = t->c_light;
+	rs.rt.c_hat = t->c_hat;
+	rs.rt.radiation_constant = t->radiation_constant;
+	rs.rt.Erad_floor = t->Erad_floor;
+	rs.rt.beta_order = t->beta_order;
+	rs.rt.pow_mode = t->pow_mode;
+	rs.rt.eddington_model = t->eddington_model;
+	rs.eos.tr.gamma = t->gamma;
+	rs.eos.tr.mean_molecular_weight = t->mean_molecular_weight;
+	rs.eos.tr.boltzmann_constant = t->boltzmann_constant;
+	rs.nstartHyperbolic_ = 6;
+	rs.ndim = 3;
+	rs.ComputePlanckOpacity = closedOpacity(*t, t->kappaP);
+	rs.ComputeEnergyMeanOpacity = closedOpacity(*t, t->kappaE);
+	rs.ComputeFluxMeanOpacity = closedOpacity(*t, t->kappaF);
+	long tot[7] = {0, 0, 0, 0, 0, 0, 0};
+	Box one; // lo = hi = (0, 0, 0)
+	_Pragma("omp parallel")
+	{
+		long mine[7] = {0, 0, 0, 0, 0, 0, 0};
+		_Pragma("omp for schedule(dynamic, 64)")
+		for (long i = 0; i < n; ++i) {
+			double cell[10];
+			for (int c = 0; c < 10; ++c) {
+				cell[c] = U[c * n + i];
+			}
+			int it[4] = {0, 0, 0, 0}, fail[3] = {0, 0, 0};
+			rs.AddSourceTermsSingleGroup(Array4<double>(cell, one, 10), Array4<const double>(src + i, one, 1), one, dt_radiation, stage, it, fail);
+			for (int c = 0; c < 10; ++c) {
+				U[c * n + i] = cell[c];
+			}
+			per_cell[0 * n + i] = it[0];
+			per_cell[1 * n + i] = it[1];
+			per_cell[2 * n + i] = it[2];
+			per_cell[3 * n + i] = fail[0];
+			per_cell[4 * n + i] = fail[2];
+			mine[0] += it[0];
+			mine[1] += it[1];
+			mine[2] = std::max(mine[2], static_cast<long>(it[2]));
+			mine[3] += it[3];
+			for (int c = 0; c < 3; ++c) {
+				mine[4 + c] += fail[c];
+			}
+		}
+		_Pragma("omp critical")
+		for (int c = 0; c < 7; ++c) {
+			tot[c] = (c == 2) ? std::max(tot[c], mine[c]) : tot[c] + mine[c];
+		}
+	}
+	for (int c = 0; c < 7; ++c) {
+		totals[c] = tot[c];
+	}
+}
+
 } // extern "C"

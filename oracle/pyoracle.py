@@ -60,6 +60,15 @@ def traits(gamma=1.4, reconstruct_eint=True, ndim=3, nscalars=0, mean_molecular_
     return HydroTraits(gamma, cs_isothermal, mean_molecular_weight, boltzmann_constant, int(reconstruct_eint), nscalars, ndim)
 
 
+class RadCellTraits(C.Structure):
+    """orc_rad_cell_traits: what the matter-radiation exchange reads of qk_rad_traits / qk_hydro_traits (gamma == 1: isothermal)"""
+    _fields_ = [("c_light", C.c_double), ("c_hat", C.c_double), ("radiation_constant", C.c_double), ("Erad_floor", C.c_double),
+                ("kappaP", C.c_double), ("kappaE", C.c_double), ("kappaF", C.c_double),
+                ("opacity_T_ref", C.c_double), ("opacity_T_exponent", C.c_double), ("opacity_pow_floor", C.c_double),
+                ("gamma", C.c_double), ("mean_molecular_weight", C.c_double), ("boltzmann_constant", C.c_double),
+                ("beta_order", C.c_int), ("opacity_model", C.c_int), ("pow_mode", C.c_int), ("eddington_model", C.c_int)]
+
+
 class SimConfig(C.Structure):
     _fields_ = [
         ("problem", C.c_int),
@@ -151,6 +160,26 @@ class Oracle:
         L.orc_planck_function.argtypes, L.orc_planck_function.restype = [D, D, D, D, D], D
         L.orc_group_mean_opacity.argtypes = [C.c_int, DP, DP, DP, DP, DP]
         L.orc_rad_quantity_exponents.argtypes = [C.c_int, DP, DP, DP]
+
+    # ---------------------------------------------------------------- the matter-radiation exchange, cell by cell
+    def rad_source_cells(self, t: RadCellTraits, U: np.ndarray, src: np.ndarray, dt_radiation: float, stage: int):
+        """AddSourceTermsSingleGroup on every cell of U[10, n] as a box of its own.  Returns (U after, record, totals): record is a dict of int32
+        arrays over the cells — solves, newton (iterations summed over the solves, n + 1 each), newton_max, fail_newton, fail_outer —, totals
+        the counters in the layout of the C-ABI: iteration counter [0..3], failure counter [0..2]"""
+        U = np.ascontiguousarray(U, dtype=np.float64).copy()
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        n = U.shape[1]
+        assert U.shape == (10, n) and src.shape == (n,)
+        rec = np.zeros((5, n), dtype=np.int32)
+        tot = (C.c_long * 7)()
+        f = self.lib.orc_rad_source_cells
+        f.argtypes = [C.POINTER(RadCellTraits), C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_int),
+                      C.POINTER(C.c_long)]
+        f.restype = None
+        self.lib.orc_set_num_threads(int(max(1, min(usable_cores(), n // 512))))
+        f(C.byref(t), n, _dp(U), _dp(src), float(dt_radiation), int(stage), rec.ctypes.data_as(C.POINTER(C.c_int)), tot)
+        keys = ("solves", "newton", "newton_max", "fail_newton", "fail_outer")
+        return U, dict(zip(keys, rec)), [int(v) for v in tot]
 
     # ---------------------------------------------------------------- multigroup helper functions
     def planck_integral(self, x: float) -> float:

@@ -2,7 +2,38 @@
 #include <algorithm>
 #include <cstring>
 
+#include "qk_device.hpp"
 #include "qk_internal.hpp"
+
+namespace
+{
+
+// qk_arith_evaluate: the division and square-root primitives of qk_device.hpp themselves, element by element
+__global__ void __launch_bounds__(256) k_arith_evaluate(int what, int64_t n, const double *a, const double *b, double *out)
+{
+	const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+	if (i >= n) {
+		return;
+	}
+	double r;
+	switch (what) {
+	case QK_ARITH_DIVBY_RECIPOF:
+		r = qk::divBy(a[i], qk::recipOf(b[i]));
+		break;
+	case QK_ARITH_DIVN:
+		r = qk::divN(a[i], b[i]);
+		break;
+	case QK_ARITH_RECIPEXACT:
+		r = qk::recipExact(b[i]);
+		break;
+	default:
+		r = qk::sqrtN(a[i]);
+		break;
+	}
+	out[i] = r;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -205,6 +236,22 @@ int qk_upload_array4_table(qk_ctx *ctx, int n, const qk_array4 *host_table, qk_a
 int qk_upload_iarray4_table(qk_ctx *ctx, int n, const qk_iarray4 *host_table, qk_iarray4 **device_table)
 {
 	return uploadTable(ctx, n, host_table, sizeof(qk_iarray4), reinterpret_cast<void **>(device_table));
+}
+
+int qk_arith_evaluate(qk_ctx *ctx, qk_stream s, int what, int64_t n, const double *d_a, const double *d_b, double *d_out)
+{
+	if (ctx == nullptr) {
+		return QK_ERR_INVALID;
+	}
+	QK_REQUIRE(ctx, what >= QK_ARITH_DIVBY_RECIPOF && what <= QK_ARITH_SQRTN, "arith_evaluate: unknown function");
+	QK_REQUIRE(ctx, d_out != nullptr && (d_a != nullptr || what == QK_ARITH_RECIPEXACT) && (d_b != nullptr || what == QK_ARITH_SQRTN),
+		   "arith_evaluate: NULL argument");
+	if (n <= 0) {
+		return QK_OK;
+	}
+	hipLaunchKernelGGL(k_arith_evaluate, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(s), what, n, d_a, d_b, d_out);
+	const hipError_t e = hipGetLastError();
+	return (e == hipSuccess) ? QK_OK : qk::setError(ctx, QK_ERR_HIP, "arith_evaluate", hipGetErrorString(e));
 }
 
 } // extern "C"

@@ -89,12 +89,17 @@ QK_DEV auto unit(int axis, int comp) -> int { return axis == comp ? 1 : 0; }
 // div_fixup  — 11 instructions, one of them quarter rate, in one dependency chain.  The Riemann solver divides 4 numerators
 // by rho_L, 4 by rho_R, 2 + 2 by (gamma-1) rho and 6 by S_K - S*: with the reciprocal refined once per denominator every
 // further quotient is mul + 2 fma, the SAME three operations on the SAME operands as the tail of the expansion, hence the
-// same bits whenever div_scale does not rescale and div_fixup does not intervene: denominator and quotient in the normal
-// range (roughly |d|, |n / d| in [2^-1020, 2^1020] with exponents of n and d less than 768 apart).  Outside it: a zero
-// quotient may come out as +0 where IEEE gives -0; a zero, infinite or subnormal DENOMINATOR (rho, (gamma-1) rho, S_K - S*)
-// yields NaN where IEEE gives +-inf or a rounded subnormal quotient — such a state is invalid in the reference as well (the
-// cell is flagged and the step retried), it just fails with a different non-number.  A per-face range guard with a plain-
-// division fallback was measured: the second code path costs more than the shared reciprocals save.
+// same bits whenever div_scale does not rescale and div_fixup does not intervene.  Measured on an MI355X against IEEE division
+// (tests/test_arith_primitives_gpu.py: 2^16 random pairs per exponent, exponents walked outward in steps of 8 binades): no
+// difference for |d| and |n| from 2^-1004 to 2^1020 and |n / d| from 2^-1004 to 2^1020 (the ends of the walk at the top); the first
+// one at 2^-1012, where the residual fma(-d, q, n), 53 binades below n, has run out of subnormal bits.  The range relied on, and
+// asserted bit for bit by that test, lies 16 binades inside: |d|, |n| and |n / d| in [2^-996, 2^1004].  Outside it: a zero
+// quotient may come out as +0 where IEEE gives -0; a zero or infinite DENOMINATOR (rho, (gamma-1) rho, S_K - S*) yields NaN where
+// IEEE gives +-inf or 0, a subnormal one NaN or a quotient that is not correctly rounded; an INFINITE NUMERATOR yields NaN where
+// IEEE keeps the infinity (fma(-d, inf, inf)) — such a state is invalid in the reference as well (the cell is flagged and the step
+// retried), it just fails with a different non-number.  Where the reference BRANCHES on such a value the call site restores it
+// (workOverCC in qk_rad_device.hpp: `inf <= inf` ends the outer iteration of the matter-radiation exchange).  A per-face range
+// guard with a plain-division fallback was measured: the second code path costs more than the shared reciprocals save.
 struct Recip {
 	double d, r;
 };
@@ -119,7 +124,8 @@ QK_DEV auto divBy(double n, Recip const &R) -> double
 // Correctly rounded FP64 square root without the range scaling of hipcc's expansion.  `sqrt(x)` compiles to 22 VALU instructions: compare
 // against 2^-767, select a scale, ldexp, v_rsq_f64, two multiplies and seven fma of Goldschmidt / Newton refinement, ldexp back, and the class test
 // that returns x itself for +-0 and +inf.  The seven-instruction tail around the refinement only serves arguments below 2^-767 (1e-231): no
-// density, c_s^2 or v^2 of a valid state comes near.  This is the same refinement on the same operands (the same bits for x >= 2^-767) plus the
+// density, c_s^2 or v^2 of a valid state comes near.  This is the same refinement on the same operands (the same bits for x >= 2^-767; measured on an
+// MI355X, tests/test_arith_primitives_gpu.py: the bits of IEEE sqrt down to 2^-1004, first difference at 2^-1012; relied on from 2^-996 up) plus the
 // class test — sqrt(0) = 0 matters: |v| of gas at rest —, 15 instructions; a PPM + HLLC face takes seven square roots.
 QK_DEV auto sqrtN(double x) -> double
 {

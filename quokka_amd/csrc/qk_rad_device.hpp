@@ -313,6 +313,15 @@ QK_DEV auto egasFromEint(Recip const &Rrho, double px, double py, double pz, dou
 	return Eint + 0.5 * divBy(px * px + py * py + pz * pz, Rrho);
 }
 
+// n / c^2 of the work term.  divBy turns an infinite numerator into NaN where the reference's division keeps the infinity, and the reference branches
+// on it: |work - work_prev| <= 1e-8 |work| holds for inf <= inf and ends the outer iteration WITHOUT an outer-iteration failure (a cell whose
+// momentum and flux have overflowed, tests/test_rad_source_cells_gpu.py).  c^2 is positive and finite: inf / c^2 is the numerator itself.
+QK_DEV auto workOverCC(double n, Recip const &Rc2) -> double
+{
+	const double q = divBy(n, Rc2);
+	return __builtin_isinf(n) ? n : q;
+}
+
 // source_terms_single_group.hpp:29-563 for one cell.  U[10] in place; counters as in the reference:
 // it_counter[0] += 1, [1] += n+1, [2] = max(n+1); fail[0] Newton failure, fail[2] outer-iteration failure.
 // radiation_system.hpp:1420-1483 (nGroups_ == 1) with BackwardEulerOneVariable (:1387-1418): the dust temperature between gas and radiation
@@ -464,7 +473,7 @@ QK_DEV void radSourceCell(RadT const &r, Eos const &eos, double U[10], double sr
 					kappaF = r.template kappaF<TDEP>(rho, T_d);
 					if (beta_order != 0) { // include_work_term_in_source = true
 						if (ite == 0) {
-							work = divBy((x1GasMom0 * Frad_t0[0] + x2GasMom0 * Frad_t0[1] + x3GasMom0 * Frad_t0[2]) * (2.0 * kappaE - kappaF) * chat, Rc2) *
+							work = workOverCC((x1GasMom0 * Frad_t0[0] + x2GasMom0 * Frad_t0[1] + x3GasMom0 * Frad_t0[2]) * (2.0 * kappaE - kappaF) * chat, Rc2) *
 							       lorentz_factor_v * dt;
 						}
 					}
@@ -655,7 +664,7 @@ QK_DEV void radSourceCell(RadT const &r, Eos const &eos, double U[10], double sr
 			break;
 		}
 		work_prev = work;
-		work = divBy((x1GasMom1 * Frad_t1[0] + x2GasMom1 * Frad_t1[1] + x3GasMom1 * Frad_t1[2]) * chat, Rc2) * lorentz_factor_v * (2.0 * kappaE - kappaF) * dt;
+		work = workOverCC((x1GasMom1 * Frad_t1[0] + x2GasMom1 * Frad_t1[1] + x3GasMom1 * Frad_t1[2]) * chat, Rc2) * lorentz_factor_v * (2.0 * kappaE - kappaF) * dt;
 		const double lag_tol = 1.0e-13;
 		if ((fabs(work) == 0.0) || (cscale * fabs(work - work_prev) < lag_tol * Etot0) || (fabs(work - work_prev) <= lag_tol * R) ||
 		    (fabs(work - work_prev) <= 1.0e-8 * fabs(work))) {
