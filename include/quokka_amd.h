@@ -264,6 +264,14 @@ typedef struct qk_hydro_stage_args {
 				  * pass: a step in which either stage counts flagged cells is redone without the hand-off (U_old is untouched by both stages). */
 	int prim_in;		 /* stage 2 only.  1: U_in holds what a stage 1 with prim_out stored: the pre-pass and the three sweeps read their primitives
 				  * instead of converting the conserved state four times over (4.9 conversions per cell); same bytes, same bits. */
+	int store_vel_rk2;	 /* stage 2 of the exact form (rk2_carry_rhs == 0) only: write the settled face velocity of every face the stage evaluates —
+				  * avgFaceVel = 0.5 v1 + 0.5 v2 (reference src/QuokkaSimulation.hpp:1107, :1221), in a correction pass (fofc_pass) the
+				  * first-order face velocity on the faces it replaces (replaceFluxes(avgFaceVel, FOfaceVel, redoFlag), :1248) — into velRk2[d]:
+				  * what AdvectWithUmac moves the tracer particles with.  The first pass and the correction pass each write EVERY face
+				  * stage 1 wrote in halfVel (each box's high face included), so the arrays are complete after either.  Refused with
+				  * rk2_carry_rhs (the carried form has no halfVel) and in stage 1.  0: velRk2 is neither read nor required. */
+	qk_array4 *velRk2[3];	 /* face-centred like halfVel, 1 component, no ghost faces; required for d < ndim when store_vel_rk2 != 0.  Separate from
+				  * halfVel for the reason fluxRk2 is separate from halfFlux: both evaluations of a tile-boundary face need v1 intact */
 } qk_hydro_stage_args;
 
 /* One RK stage of advanceHydroAtLevel (reference src/QuokkaSimulation.hpp:1099-1198 / 1202-1287) WITHOUT the

@@ -4,7 +4,9 @@ time of operator-path steps of the same run taken with do_tracers = 0 (the parti
 five steps with tracers and five without, alternating.  The step
 with tracers also pays the snapshot the retry loop takes (a clone of every particle array) and one device -> host read in Redistribute: the tool
 reports the step times so that the difference shows them.
-Prints one JSON line; profiles/tracers/README.md keeps the results.     python profiles/tools/tracer_time.py [n steps]"""
+--fused-stages: the same on the fused kernels with HydroSimulation.tracers_on_fused_stages = 1 (stage 2 stores avgFaceVel itself); the step
+without tracers is then the exact-form fused step, and the keys that say "operator" hold the fused figures ("path" tells which).
+Prints one JSON line; profiles/tracers/README.md keeps the results.     python profiles/tools/tracer_time.py [n steps] [--fused-stages]"""
 import json
 import os
 import sys
@@ -17,11 +19,14 @@ from bench import read_profile  # noqa: E402
 from quokka_amd.multifab import Context  # noqa: E402
 from quokka_amd.simulation import sedov_problem  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+fused_stages = "--fused-stages" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--fused-stages"]
+n = int(argv[0]) if len(argv) > 0 else 256
+steps = int(argv[1]) if len(argv) > 1 else 200
 ctx = Context(0)
 L = ctx.L
-sim = sedov_problem(ctx, n, max_grid_size=min(n, 128), use_fused=False)
+sim = sedov_problem(ctx, n, max_grid_size=min(n, 128), use_fused=fused_stages)
+sim.tracers_on_fused_stages = int(fused_stages)
 sim.do_tracers = 1
 sim.InitTracerParticles()
 np0 = sim.tracers.num_particles
@@ -71,4 +76,4 @@ rows = [sample("from step 1, cell order")]  # (the first step also pays the firs
 while sim.istep < steps:
     assert sim.step()
 rows.append(sample(f"after {steps} steps"))
-print(json.dumps({"n": n, "boxes": sim.lev.nboxes, "particles_at_start": np0, "samples": rows}))
+print(json.dumps({"path": "fused stages, exact form" if fused_stages else "operators", "n": n, "boxes": sim.lev.nboxes, "particles_at_start": np0, "samples": rows}))

@@ -89,6 +89,10 @@ struct SweepArgs {
 	// (rho, v, P, E_int) of the cell it completes — consToPrim of the state it would have stored, whose quotients its limits already formed — and
 	// every kernel of stage 2 reads its input as primitives: no conversion in the pre-pass, the three sweeps (4.9 per cell and stage), same bytes
 	bool prim_in, prim_out;
+	// exact form, stage 2 (qk_hydro_stage_args::store_vel_rk2): write the settled face velocity — 0.5 v1 + 0.5 v2, first-order on the faces a correction
+	// pass replaces — to rk2Vel (never over v1, for the reason rk2Flux is never F1).  Last in the struct: the offsets the carried form reads stay
+	bool store_vel;
+	qk_array4 *rk2Vel; // of this sweep's direction
 };
 
 QK_DEV auto sarr(SweepArgs const &a, int comp) -> double * { return a.scratch + static_cast<int64_t>(comp) * a.total_cells; }
@@ -524,7 +528,8 @@ template <int STAGE, int NV> QK_DEV void maskedFaceFlux(SweepArgs const &a, int 
 //   exact, stage 1   halfFlux / halfVel receive F1 (in the FOFC pass they keep the UNCORRECTED flux the first pass stored: flux_rk2 is formed from
 //                    it, QuokkaSimulation.hpp:1105-1108);
 //   exact, stage 2   flux_rk2 = (0 + 0.5 F1) + 0.5 F2 (QuokkaSimulation.hpp:1106, :1220) replaces F, and goes to rk2Flux on request (never over F1:
-//                    tile-boundary faces of the x sweep are evaluated twice);
+//                    tile-boundary faces of the x sweep are evaluated twice); likewise vf = 0.5 v1 + 0.5 v2 goes to rk2Vel on request (store_vel_rk2:
+//                    avgFaceVel, what the tracer particles are advected with), in the first pass and in the FOFC pass alike — each writes every face;
 //   FOFC pass        a face that touches a cell the first pass flagged (redoFlag carries one filled ghost cell) takes the first-order flux of the old
 //                    state instead — replaceFluxes (QuokkaSimulation.hpp:1324-1368), in stage 2 flux_rk2 of the face as a whole.  In stage 1 the old
 //                    state is the input state and the caller holds its primitives (qLo, qRo); stage 2 converts the two cells of U_old.
@@ -598,6 +603,10 @@ QK_DEV void settleFace(SweepArgs const &a, Eos const &eos, int ndim, int b, cons
 		for (int n = 0; n < NV; ++n) {
 			RF.p[o2 + RF.ns * n] = F[n];
 		}
+	}
+	if (STAGE == 2 && a.store_vel && live) { // avgFaceVel of the reference (QuokkaSimulation.hpp:1107, :1221, :1248): what AdvectWithUmac moves the tracers with
+		WA4 RV(a.rk2Vel[b]);
+		RV(fi[0], fi[1], fi[2]) = vf;
 	}
 }
 
@@ -1458,6 +1467,7 @@ auto sweepArgsFor(SweepArgs a, const qk_hydro_stage_args *args, int d) -> SweepA
 	a.halfFlux = args->halfFlux[d];
 	a.halfVel = args->halfVel[d];
 	a.rk2Flux = args->fluxRk2[d];
+	a.rk2Vel = args->velRk2[d];
 	a.inv_dx = 1.0 / args->dx[d];
 	a.dx = args->dx[d];
 	return a;
@@ -1628,6 +1638,15 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 			   "qk_hydro_stage_fused: store_flux_rk2 needs fluxRk2[d], distinct from halfFlux[d]");
 		QK_REQUIRE(ctx, lev->maxlen[d] >= 1, "qk_hydro_stage_fused: empty box");
 	}
+	if (args->store_vel_rk2 != 0) {
+		QK_REQUIRE(ctx, args->rk2_carry_rhs == 0, "qk_hydro_stage_fused: store_vel_rk2 excludes rk2_carry_rhs (the carried form has no halfVel to average with)");
+		QK_REQUIRE(ctx, args->stage == 2, "qk_hydro_stage_fused: store_vel_rk2 belongs to stage 2 (stage 1 leaves its face velocity in halfVel)");
+		for (int d = 0; d < t->ndim; ++d) {
+			QK_REQUIRE(ctx, args->velRk2[d] != nullptr, "qk_hydro_stage_fused: store_vel_rk2 needs velRk2[d]");
+			QK_REQUIRE(ctx, args->velRk2[d] != args->halfVel[d],
+				   "qk_hydro_stage_fused: store_vel_rk2 needs velRk2[d] distinct from halfVel[d] (the x sweep evaluates a tile-boundary face in both tiles, and both need v1 intact)");
+		}
+	}
 	QK_REQUIRE(ctx, args->scratch_bytes >= qk_hydro_stage_scratch_bytes(lev, t), "qk_hydro_stage_fused: scratch too small");
 	if (args->prim_in != 0 || args->prim_out != 0) {
 		QK_REQUIRE(ctx, t->reconstruct_eint == 0 && !Eos(*t).isothermal && t->eos_temperature_model == 0,
@@ -1681,6 +1700,7 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 	a.use_dual_energy = args->use_dual_energy;
 	a.reconstruct_eint = re;
 	a.store_rk2 = (args->store_flux_rk2 != 0);
+	a.store_vel = (args->store_vel_rk2 != 0);
 	a.rhs1 = args->rhs1;
 	a.fluxMask = (args->rk2_carry_rhs != 0) ? args->flux_mask : nullptr;
 	a.prim_in = (args->prim_in != 0);

@@ -294,6 +294,10 @@ class HydroSimulation:
         # particle per cell (quokka_amd/tracers.py).  0: nothing is allocated, nothing is launched.
         self.do_tracers = 0
         self.tracers = None
+        # 1: a run with tracers keeps both RK stages on the fused kernels (use_fused), whose stage 2 then stores avgFaceVel itself
+        # (qk_hydro_stage_args::store_vel_rk2; _tracers_on_fused).  0 (default): with tracers both stages take the reference-shaped operators.
+        self.tracers_on_fused_stages = 0
+        self._avg_face_vel = None  # the face arrays that hold avgFaceVel of the stage-2 attempt that stood: set where a stage 2 is finished
         self.min_overlap_cells = 8 * 128 ** 3
         # the fused stage is instantiated for 0..3 passive scalars; mass scalars (consistent multi-fluid advection) take the operator path
         # (1-D / 2-D builds: the x sweep resp. the y sweep carries the epilogue; the carried-rhs form of the RK2 average is a 3-D instantiation)
@@ -554,6 +558,7 @@ class HydroSimulation:
     def _stage_unfused(self, stage: int, U_in, U_old, U_out, dt, with_fofc: bool) -> bool:
         """One stage exactly as reference src/QuokkaSimulation.hpp:1099-1198 (stage 1) / 1202-1287 (stage 2)."""
         self._unfused_ran = True
+        self.counters["operator_stages"] = self.counters.get("operator_stages", 0) + 1  # (stages taken on the reference-shaped operators)
         t, lev, nd = self._tmp(), self.lev, self.geom.ndim
         self.computeHydroFluxes(U_in, t["flux"], t["vel"])
         if stage == 1:
@@ -583,6 +588,8 @@ class HydroSimulation:
             if nbad > 0 and self.abortOnFofcFailure_ != 0:
                 return False
         self._limits_and_sync(U_out)
+        if stage == 2:
+            self._avg_face_vel = vl  # avgFaceVel, first-order on the faces a correction replaced (QuokkaSimulation.hpp:1248)
         if stage == 2 and self._needs_flux_rk2():
             for d in range(nd):  # what the flux registers accumulate (possibly FOFC-corrected), where the fused stage leaves it
                 self.fluxRk2()[d].copy_from(fl[d])
@@ -606,7 +613,21 @@ class HydroSimulation:
         """the carried-right-hand-side form of the RK2 average (qk_hydro_stage_args::rk2_carry_rhs; `rk2_carry_rhs` attribute, default off):
         only where nothing consumes flux_rk2 (no flux registers) and the integrator has two stages"""
         return (bool(getattr(self, "rk2_carry_rhs", False)) and self.integratorOrder_ == 2 and not getattr(self, "store_flux_rk2", False)
-                and self.geom.ndim == 3 and not getattr(self, "_force_exact_form", False))
+                and self.geom.ndim == 3 and not getattr(self, "_force_exact_form", False) and not self._tracers_on_fused())
+
+    def _tracers_on_fused(self) -> bool:
+        """`tracers_on_fused_stages` with tracers present and the fused kernels in use: both RK stages stay on the fused kernels and every fused
+        stage 2 stores avgFaceVel in velRk2() (qk_hydro_stage_args::store_vel_rk2).  Only the exact form has the stage-1 face velocity to average
+        with, so such a run is taken in the exact form whatever `rk2_carry_rhs` says (_carry_active): a tracer run is the form that is
+        bit-identical to the reference-shaped operators, not the carried one."""
+        return bool(self.tracers_on_fused_stages) and self.use_fused and bool(self.do_tracers) and self.tracers is not None
+
+    def velRk2(self):
+        """avgFaceVel = 0.5 v1 + 0.5 v2 as the last fused stage 2 with store_vel_rk2 left it (first-order on the faces its correction pass
+        replaced); allocated on first use; separate from halfVel (v1), which both evaluations of a tile-boundary face of the x sweep must find intact"""
+        if getattr(self, "_velRk2", None) is None:
+            self._velRk2 = [MultiFab(self.lev, 1, 0, facedir=d, fill=0.0) for d in range(self.geom.ndim)]
+        return self._velRk2
 
     def rhs1(self):
         """div F1 and div v1 per cell, written by stage 1 and read by stage 2 in the carried-rhs mode"""
@@ -669,6 +690,10 @@ class HydroSimulation:
         if a.store_flux_rk2 or a.flux_mask:
             for d in range(nd):
                 a.fluxRk2[d] = tab(self.fluxRk2()[d])
+        if stage == 2 and self._tracers_on_fused():  # avgFaceVel for AdvectWithUmac: the first pass and the correction pass each write every face
+            a.store_vel_rk2 = 1
+            for d in range(nd):
+                a.velRk2[d] = tab(self.velRk2()[d])
         a.fofc_pass = int(fofc)
         if self._prim_now and not fofc:  # the primitive hand-off between the two stages of this advance (prim_handoff)
             a.prim_out, a.prim_in = int(stage == 1), int(stage == 2)
@@ -746,8 +771,15 @@ class HydroSimulation:
     def _finish_stage(self, stage, U_in, U_old, U_out, dt, nbad: int) -> bool:
         if nbad == 0:
             self._stage1_left_F1 = (stage == 1 and not self._carry_active())
+            self._fused_stage_stood(stage)
             return True
         return self._correct_stage(stage, U_in, U_old, U_out, dt)
+
+    def _fused_stage_stood(self, stage: int):
+        """a fused stage (first pass or correction pass) is finished and its result stands: after a stage 2 that stored avgFaceVel, velRk2()
+        is what the tracers are advected with"""
+        if stage == 2 and self._tracers_on_fused():
+            self._avg_face_vel = self.velRk2()
 
     def _fill_and_stage(self, stage, U_in, U_old, U_out, dt, fused: Optional[bool] = None) -> bool:
         """fillBoundaryConditions(U_in) + one RK stage, its redo count read back (fused = False: on the reference-shaped operators whatever use_fused)"""
@@ -791,6 +823,7 @@ class HydroSimulation:
         self._fused_begin(stage)
         self._fused_launch(stage, U_in, U_old, U_out, dt, fofc=True)
         nbad = self._fused_end(stage)
+        self._fused_stage_stood(stage)
         return not (nbad > 0 and self.abortOnFofcFailure_ != 0)
 
     def _fofc_stage2_of_carried_form(self, U_in, U_old, U_out, dt) -> bool:
@@ -847,11 +880,13 @@ class HydroSimulation:
         self._signal_of_state_new = None  # state_new_cc_ is about to be overwritten
         self._err_latched, self._unfused_ran = False, False
         # with tracer particles both stages take the reference-shaped operators, which form avgFaceVel = 0.5 v1 + 0.5 v2 face by face, first-order
-        # corrections included (reference src/QuokkaSimulation.hpp:1061-1073, :1107, :1221, :1248): the fused stage 2 does not store its face velocity
+        # corrections included (reference src/QuokkaSimulation.hpp:1061-1073, :1107, :1221, :1248) — or, with tracers_on_fused_stages, stay on the
+        # fused kernels in the exact form, whose stage 2 then stores the same values (_tracers_on_fused)
         with_tracers = bool(self.do_tracers) and self.tracers is not None
         if with_tracers:
             self._check_tracers()
-        fused = self.use_fused and not with_tracers
+        fused = self.use_fused and (not with_tracers or self._tracers_on_fused())
+        self._avg_face_vel = None
         pair_done = False
         self._prim_now = False
         if getattr(self, "_prim_backoff", 0) > 0:  # (a recent attempt was dropped: see below)
@@ -872,6 +907,7 @@ class HydroSimulation:
             latched = self._err_latched
             if self._fused_end(1, 0, vals) == 0 and self._fused_end(2, 1, vals) == 0:
                 self._stage1_left_F1 = not self._carry_active()
+                self._fused_stage_stood(2)
                 pair_done = True
                 self._prim_backoff_len = 0
             else:
@@ -914,7 +950,10 @@ class HydroSimulation:
             raise capi.QkError("density is negative in SyncDualEnergy! abort!! (reference src/hydro/hydro_system.hpp:834-836)")
         if with_tracers:
             # AdvectWithUmac(avgFaceVel, lev, dt) (reference src/QuokkaSimulation.hpp:1290-1314): after stage 2, before the second Strang half-step
-            self.tracers.advect(self._tmp()["rk2vel"], dt_lev)
+            # on avgFaceVel of the stage-2 attempt that stood: the operators' (also a stage 2 redone on them) or the fused stage's own
+            if self._avg_face_vel is None:
+                raise capi.QkError("do_tracers: no stage 2 of this advance left avgFaceVel behind")
+            self.tracers.advect(self._avg_face_vel, dt_lev)
         if self.strang_sources:
             ok = self._strang_sources(self.state_new_cc_, time + dt_lev, 0.5 * dt_lev)
             self._signal_of_state_new = None  # the sources changed the energies: the signal speeds FixupState left no longer describe the state

@@ -68,7 +68,8 @@ class TracerParticles:
                                             C.c_void_p(self.cpu.data_ptr()), int(first_id), int(self.sim.rank)), "qk_tracer_InitOnePerCell")
 
     def advect(self, umac: Sequence[MultiFab], dt: float):
-        """AdvectWithUmac(umac, lev, dt): umac[d] face-centred in d, one component, no ghost faces"""
+        """AdvectWithUmac(umac, lev, dt): umac[d] face-centred in d, one component, no ghost faces.  The driver hands over avgFaceVel of the
+        stage-2 attempt that stood (HydroSimulation._avg_face_vel): the operators' rk2vel, or velRk2 of the fused stage 2 (tracers_on_fused_stages)"""
         assert len(umac) >= self.ndim
         for d in range(self.ndim):
             assert umac[d].facedir == d and umac[d].ncomp == 1 and umac[d].nghost == 0 and umac[d].level is self.lev
