@@ -714,4 +714,136 @@ void orc_rad_source_cells(orc_rad_cell_traits const *t, long n, double *U, doubl
 	}
 }
 
+// ------------------------------------------------------------------ the multigroup matter-radiation exchange, cell by cell
+// The fields of qk_rad_traits / qk_hydro_traits (include/quokka_amd.h) the multigroup exchange reads, as a closed set.  gamma == 1: isothermal.
+struct orc_rad_mg_cell_traits {
+	double c_light, c_hat, radiation_constant, Erad_floor;
+	double energy_unit;
+	double rad_boundaries[9], mg_kappa_exponent[9], mg_kappa_lower[9];
+	double mg_kappa_rho_exponent, mg_kappa_T_ref, mg_kappa_T_exponent;
+	double dust_gas_interaction_coeff, gas_dust_coupling_threshold;
+	double cooling_linear_coeff[8], cr_heating_rate, pe_heating_E1_derivative;
+	double gamma, mean_molecular_weight, boltzmann_constant;
+	int beta_order, eddington_model, pow_mode, ngroups, mg_opacity_model;
+	int enable_dust_gas_thermal_coupling_model, thermal_model, enable_photoelectric_heating;
+};
+
+// seed == 0 (the default): the multigroup path calls libm as it is.  Otherwise the results of pow, exp, log and log10 in radiation_multigroup.hpp
+// (the Planck-integral lookup included) and in the opacity hook below are moved by up to `ulps` ulps (radiation_multigroup.hpp, namespace diag).
+// Single-group radiation, cooling and hydro never see it.
+void orc_set_libm_jitter(unsigned long long seed, int ulps)
+{
+	diag::jitter_seed = seed;
+	diag::jitter_ulps = ulps;
+}
+
+// AddSourceTermsMultiGroup on each of n cells as a box of its own.  U[6 + 4 ng][n] (component outermost) is updated in place, src[ng][n] is the
+// radiation energy source.  per_cell[8][n]: solves, Newton iterations summed over the solves (n + 1 per solve), the largest n + 1 of one solve,
+// Newton failures, outer-iteration failures, negative dust temperatures, decoupled solves, the branch mask (diag::Branch).
+// totals[7]: p_iteration_counter[0..3] then p_iteration_failure_counter[0..2], the layout of the C-ABI.
+void orc_rad_mg_source_cells(orc_rad_mg_cell_traits const *t, long n, double *U, double const *src, double dt_radiation, int stage, int *per_cell, long *totals)
+{
+	RadSystem rs;
+	rs.rt.c_light = t->c_light;
+	rs.rt.c_hat = t->c_hat;
+	rs.rt.radiation_constant = t->radiation_constant;
+	rs.rt.Erad_floor = t->Erad_floor;
+	rs.rt.beta_order = t->beta_order;
+	rs.rt.pow_mode = t->pow_mode;
+	rs.rt.eddington_model = t->eddington_model;
+	rs.rt.nGroups = t->ngroups;
+	rs.rt.opacity_model = t->mg_opacity_model;
+	rs.rt.energy_unit = t->energy_unit;
+	rs.rt.radBoundaries.assign(t->rad_boundaries, t->rad_boundaries + t->ngroups + 1);
+	rs.rt.enable_dust_gas_thermal_coupling_model = (t->enable_dust_gas_thermal_coupling_model != 0);
+	rs.rt.dustGasInteractionCoeff = t->dust_gas_interaction_coeff;
+	rs.rt.gas_dust_coupling_threshold = t->gas_dust_coupling_threshold;
+	rs.rt.thermal_model = t->thermal_model;
+	rs.rt.enable_photoelectric_heating = (t->enable_photoelectric_heating != 0);
+	rs.eos.tr.gamma = t->gamma;
+	rs.eos.tr.mean_molecular_weight = t->mean_molecular_weight;
+	rs.eos.tr.boltzmann_constant = t->boltzmann_constant;
+	rs.nstartHyperbolic_ = 6;
+	rs.ndim = 3;
+	const int ng = t->ngroups;
+	const orc_rad_mg_cell_traits tr = *t;
+	// include/quokka_amd.h: exponent[g] = mg_kappa_exponent[g]; lower_value[g] = mg_kappa_lower[g] * pow(rho, a) * pow(T / T_ref, b), either power
+	// with exponent 0 skipped, exponent -1 on rho a division
+	rs.DefineOpacityExponentsAndLowerValues = [tr, ng](double const *, double rho, double T, double *expo, double *lower) {
+		for (int g = 0; g < ng + 1; ++g) {
+			expo[g] = tr.mg_kappa_exponent[g];
+			double v = tr.mg_kappa_lower[g];
+			if (tr.mg_kappa_rho_exponent == -1.0) {
+				v = v / rho;
+			} else if (tr.mg_kappa_rho_exponent != 0.0) {
+				v = v * diag::pow(rho, tr.mg_kappa_rho_exponent);
+			}
+			if (tr.mg_kappa_T_exponent != 0.0) {
+				v = v * diag::pow(T / tr.mg_kappa_T_ref, tr.mg_kappa_T_exponent);
+			}
+			lower[g] = v;
+		}
+	};
+	// include/quokka_amd.h, the ISM hooks: DefineNetCoolingRate(T, n)[g] = cooling_linear_coeff[g] * T (its temperature derivative the coefficient),
+	// DefineCosmicRayHeatingRate(n) = cr_heating_rate, DefinePhotoelectricHeatingE1Derivative(T, n) = pe_heating_E1_derivative
+	rs.DefineNetCoolingRate = [tr, ng](double T, double, double *out) {
+		for (int g = 0; g < ng; ++g) {
+			out[g] = tr.cooling_linear_coeff[g] * T;
+		}
+	};
+	rs.DefineNetCoolingRateTempDerivative = [tr, ng](double, double, double *out) {
+		for (int g = 0; g < ng; ++g) {
+			out[g] = tr.cooling_linear_coeff[g];
+		}
+	};
+	rs.DefineCosmicRayHeatingRate = [tr](double) { return tr.cr_heating_rate; };
+	rs.DefinePhotoelectricHeatingE1Derivative = [tr](double, double) { return tr.pe_heating_E1_derivative; };
+	mg::MG const m(rs);
+	const int nc = 6 + 4 * ng;
+	long tot[7] = {0, 0, 0, 0, 0, 0, 0};
+	Box one; // lo = hi = (0, 0, 0)
+	_Pragma("omp parallel")
+	{
+		long mine[7] = {0, 0, 0, 0, 0, 0, 0};
+		_Pragma("omp for schedule(dynamic, 64)")
+		for (long i = 0; i < n; ++i) {
+			double cell[6 + 4 * 8], s[8];
+			for (int c = 0; c < nc; ++c) {
+				cell[c] = U[c * n + i];
+			}
+			for (int g = 0; g < ng; ++g) {
+				s[g] = src[g * n + i];
+			}
+			int it[4] = {0, 0, 0, 0}, fail[3] = {0, 0, 0};
+			diag::mask = 0;
+			m.AddSourceTermsMultiGroup(Array4<double>(cell, one, nc), Array4<const double>(s, one, ng), one, dt_radiation, stage, it, fail);
+			for (int c = 0; c < nc; ++c) {
+				U[c * n + i] = cell[c];
+			}
+			per_cell[0 * n + i] = it[0];
+			per_cell[1 * n + i] = it[1];
+			per_cell[2 * n + i] = it[2];
+			per_cell[3 * n + i] = fail[0];
+			per_cell[4 * n + i] = fail[2];
+			per_cell[5 * n + i] = fail[1];
+			per_cell[6 * n + i] = it[3];
+			per_cell[7 * n + i] = static_cast<int>(diag::mask);
+			mine[0] += it[0];
+			mine[1] += it[1];
+			mine[2] = std::max(mine[2], static_cast<long>(it[2]));
+			mine[3] += it[3];
+			for (int c = 0; c < 3; ++c) {
+				mine[4 + c] += fail[c];
+			}
+		}
+		_Pragma("omp critical")
+		for (int c = 0; c < 7; ++c) {
+			tot[c] = (c == 2) ? std::max(tot[c], mine[c]) : tot[c] + mine[c];
+		}
+	}
+	for (int c = 0; c < 7; ++c) {
+		totals[c] = tot[c];
+	}
+}
+
 } // extern "C"

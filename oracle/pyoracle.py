@@ -69,6 +69,25 @@ class RadCellTraits(C.Structure):
                 ("beta_order", C.c_int), ("opacity_model", C.c_int), ("pow_mode", C.c_int), ("eddington_model", C.c_int)]
 
 
+class RadMGCellTraits(C.Structure):
+    """orc_rad_mg_cell_traits: what the multigroup matter-radiation exchange reads of qk_rad_traits / qk_hydro_traits (gamma == 1: isothermal)"""
+    _fields_ = [("c_light", C.c_double), ("c_hat", C.c_double), ("radiation_constant", C.c_double), ("Erad_floor", C.c_double),
+                ("energy_unit", C.c_double),
+                ("rad_boundaries", C.c_double * 9), ("mg_kappa_exponent", C.c_double * 9), ("mg_kappa_lower", C.c_double * 9),
+                ("mg_kappa_rho_exponent", C.c_double), ("mg_kappa_T_ref", C.c_double), ("mg_kappa_T_exponent", C.c_double),
+                ("dust_gas_interaction_coeff", C.c_double), ("gas_dust_coupling_threshold", C.c_double),
+                ("cooling_linear_coeff", C.c_double * 8), ("cr_heating_rate", C.c_double), ("pe_heating_E1_derivative", C.c_double),
+                ("gamma", C.c_double), ("mean_molecular_weight", C.c_double), ("boltzmann_constant", C.c_double),
+                ("beta_order", C.c_int), ("eddington_model", C.c_int), ("pow_mode", C.c_int), ("ngroups", C.c_int), ("mg_opacity_model", C.c_int),
+                ("enable_dust_gas_thermal_coupling_model", C.c_int), ("thermal_model", C.c_int), ("enable_photoelectric_heating", C.c_int)]
+
+
+# the bits of the branch mask orc_rad_mg_source_cells records per cell (oracle/radiation_multigroup.hpp, diag::Branch)
+MG_BRANCHES = ("zero_tau", "dE_constrain", "denom_le_0", "alpha_gt_100", "alpha_lt_m100", "alpha_near_0", "slope_zero_mean", "slope_sign_change",
+               "slopes_frozen", "floor_clamp", "x_ge_100", "below_table", "decoupled", "negative_dust_T")
+MG_BRANCH_BIT = {name: 1 << i for i, name in enumerate(MG_BRANCHES)}
+
+
 class SimConfig(C.Structure):
     _fields_ = [
         ("problem", C.c_int),
@@ -179,6 +198,38 @@ class Oracle:
         self.lib.orc_set_num_threads(int(max(1, min(usable_cores(), n // 512))))
         f(C.byref(t), n, _dp(U), _dp(src), float(dt_radiation), int(stage), rec.ctypes.data_as(C.POINTER(C.c_int)), tot)
         keys = ("solves", "newton", "newton_max", "fail_newton", "fail_outer")
+        return U, dict(zip(keys, rec)), [int(v) for v in tot]
+
+    def set_libm_jitter(self, seed: int, ulps: int = 0):
+        """seed 0: libm as it is.  Otherwise pow / exp / log / log10 of the multigroup path move by up to `ulps` ulps, chosen by a hash of
+        (seed, function, argument bits).  Process-wide: reset to 0 after use."""
+        self.lib.orc_set_libm_jitter.argtypes = [C.c_ulonglong, C.c_int]
+        self.lib.orc_set_libm_jitter.restype = None
+        self.lib.orc_set_libm_jitter(int(seed), int(ulps))
+
+    def rad_mg_source_cells(self, t: RadMGCellTraits, U: np.ndarray, src: np.ndarray, dt_radiation: float, stage: int, jitter_seed: int = 0,
+                            jitter_ulps: int = 0):
+        """AddSourceTermsMultiGroup on every cell of U[6 + 4 ng, n] as a box of its own; src[ng, n].  Returns (U after, record, totals): record is
+        a dict of int32 arrays over the cells — solves, newton (n + 1 summed over the solves), newton_max, fail_newton, fail_outer, fail_dust,
+        decoupled, mask (MG_BRANCH_BIT) —, totals the counters in the layout of the C-ABI: iteration counter [0..3], failure counter [0..2]"""
+        ng = int(t.ngroups)
+        U = np.ascontiguousarray(U, dtype=np.float64).copy()
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        n = U.shape[1]
+        assert 2 <= ng <= 8 and U.shape == (6 + 4 * ng, n) and src.shape == (ng, n)
+        rec = np.zeros((8, n), dtype=np.int32)
+        tot = (C.c_long * 7)()
+        f = self.lib.orc_rad_mg_source_cells
+        f.argtypes = [C.POINTER(RadMGCellTraits), C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_int),
+                      C.POINTER(C.c_long)]
+        f.restype = None
+        self.lib.orc_set_num_threads(int(max(1, min(usable_cores(), n // 128))))
+        self.set_libm_jitter(jitter_seed, jitter_ulps)
+        try:
+            f(C.byref(t), n, _dp(U), _dp(src), float(dt_radiation), int(stage), rec.ctypes.data_as(C.POINTER(C.c_int)), tot)
+        finally:
+            self.set_libm_jitter(0, 0)
+        keys = ("solves", "newton", "newton_max", "fail_newton", "fail_outer", "fail_dust", "decoupled", "mask")
         return U, dict(zip(keys, rec)), [int(v) for v in tot]
 
     # ---------------------------------------------------------------- multigroup helper functions

@@ -25,6 +25,7 @@
 #include <array>
 #include <cassert>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 #include "planck_table.hpp"
@@ -32,6 +33,69 @@
 
 namespace oracle
 {
+
+// ------------------------------------------------------------------ test instrumentation of the multigroup path (not in the reference)
+// diag::mask: which of the scheme's rarely taken branches the calling thread went through since the mask was last cleared (orc_rad_mg_source_cells
+// clears it before each cell).  Recording changes no value.
+// diag::pow / exp / log / log10: the four libm functions of this file.  With jitter_seed == 0 (the default) they ARE std::pow, ...; otherwise every
+// inexact result is moved by an integer number of ulps in [-jitter_ulps, +jitter_ulps] chosen by a hash of (seed, function, argument bits):
+// deterministic, independent of the thread order, the same argument always the same result.  It models a second, equally good libm.
+namespace diag
+{
+enum Branch : unsigned {
+	ZERO_TAU = 1U << 0,	     // a group with tau <= 0: Jgg = -inf, the guess kept
+	DE_CONSTRAIN = 1U << 1,	     // enable_dE_constrain: delta_x / c_v > max(T_gas, T_rad)
+	DENOM_LE_0 = 1U << 2,	     // ComputeDiffusionFluxMeanOpacity: denom <= 0
+	ALPHA_GT_100 = 1U << 3,	     // ComputeGroupMeanOpacity
+	ALPHA_LT_M100 = 1U << 4,     //
+	ALPHA_NEAR_0 = 1U << 5,	     // |alpha| < 1e-8 (either part)
+	SLOPE_ZERO_MEAN = 1U << 6,   // ComputeRadQuantityExponents: both means zero
+	SLOPE_SIGN_CHANGE = 1U << 7, // product of the means <= 0
+	SLOPES_FROZEN = 1U << 8,     // n_iter >= max_iter_to_update_alpha_E in the full-spectrum model
+	FLOOR_CLAMP = 1U << 9,	     // ComputeThermalRadiationMultiGroup: Erad_floor
+	X_GE_100 = 1U << 10,	     // ComputePlanckEnergyFractions: x >= 100
+	BELOW_TABLE = 1U << 11,	     // integrate_planck_from_0_to_x: the series below the table
+	DECOUPLED = 1U << 12,	     // dust model 2
+	NEGATIVE_DUST_T = 1U << 13   // T_d < 0
+};
+inline thread_local unsigned mask = 0;
+inline void took(unsigned b) { mask |= b; }
+
+inline unsigned long long jitter_seed = 0;
+inline int jitter_ulps = 0;
+inline auto bitsOf(double x) -> unsigned long long
+{
+	unsigned long long u = 0;
+	std::memcpy(&u, &x, sizeof u);
+	return u;
+}
+inline auto mix(unsigned long long z) -> unsigned long long // splitmix64 finaliser
+{
+	z += 0x9e3779b97f4a7c15ULL;
+	z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+	z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+	return z ^ (z >> 31);
+}
+inline auto jittered(int fn, double a, double b, double r) -> double
+{
+	if (jitter_seed == 0 || jitter_ulps <= 0 || !std::isfinite(r) || r == 0.0) {
+		return r;
+	}
+	const unsigned long long h = mix(mix(mix(jitter_seed + static_cast<unsigned long long>(fn)) ^ bitsOf(a)) ^ bitsOf(b));
+	const long long k = static_cast<long long>(h % static_cast<unsigned long long>(2 * jitter_ulps + 1)) - jitter_ulps;
+	// finite and non-zero: the neighbouring doubles of the same sign are the neighbouring integers of the bit pattern
+	unsigned long long u = bitsOf(r);
+	u += static_cast<unsigned long long>(k);
+	double out = 0;
+	std::memcpy(&out, &u, sizeof out);
+	return std::isfinite(out) ? out : r;
+}
+// (pow with exponent 0 or 1, and every result that is exactly 0, is exact in any libm and stays as it is)
+inline auto pow(double a, double b) -> double { return (b == 0.0 || b == 1.0) ? std::pow(a, b) : jittered(0, a, b, std::pow(a, b)); }
+inline auto exp(double a) -> double { return jittered(1, a, 0.0, std::exp(a)); }
+inline auto log(double a) -> double { return jittered(2, a, 0.0, std::log(a)); }
+inline auto log10(double a) -> double { return jittered(3, a, 0.0, std::log10(a)); }
+} // namespace diag
 
 // ------------------------------------------------------------------ planck_integral.hpp
 namespace planck
@@ -67,10 +131,11 @@ inline auto integrate_planck_from_0_to_x(const double x) -> double
 		return 0.;
 	}
 	const double Y_INTERP_MIN = Y_interp[0]; // "= Y_interp[0]" (:20)
-	const double logx = std::log10(x);
+	const double logx = diag::log10(x);
 	double y = NAN;
 	if (logx < LOG_X_MIN) {
-		y = (-4 + x) * x + 8 * std::log((2 + x) / 2); // 2nd order
+		diag::took(diag::BELOW_TABLE);
+		y = (-4 + x) * x + 8 * diag::log((2 + x) / 2); // 2nd order
 		if (y > Y_INTERP_MIN) {
 			y = Y_INTERP_MIN;
 		} else if (y < 0.) {
@@ -250,6 +315,7 @@ struct MG {
 		for (int g = 0; g < nGroups_ - 1; ++g) {
 			const double x = bnd[g + 1] * energy_unit_over_kT;
 			if (x >= 100.) {
+				diag::took(diag::X_GE_100);
 				y = 1.0;
 			} else {
 				y = planck::integrate_planck_from_0_to_x(x);
@@ -275,6 +341,7 @@ struct MG {
 		auto Erad_g = power * radEnergyFractions;
 		for (int g = 0; g < nGroups_; ++g) {
 			if (Erad_g[g] < rs.Erad_floor_()) {
+				diag::took(diag::FLOOR_CLAMP);
 				Erad_g[g] = rs.Erad_floor_();
 			}
 		}
@@ -310,15 +377,17 @@ struct MG {
 			quant_mean[g] = quant[g] / (bnd[g + 1] - bnd[g]);
 			if (g > 0) {
 				if (quant_mean[g] == 0.0 && quant_mean[g - 1] == 0.0) {
+					diag::took(diag::SLOPE_ZERO_MEAN);
 					logslopes[g - 1] = 0.0;
 				} else if (quant_mean[g - 1] * quant_mean[g] <= 0.0) {
+					diag::took(diag::SLOPE_SIGN_CHANGE);
 					if (quant_mean[g] > quant_mean[g - 1]) {
 						logslopes[g - 1] = inf;
 					} else {
 						logslopes[g - 1] = -inf;
 					}
 				} else {
-					logslopes[g - 1] = std::log(std::abs(quant_mean[g] / quant_mean[g - 1])) / std::log(bin_center[g] / bin_center[g - 1]);
+					logslopes[g - 1] = diag::log(std::abs(quant_mean[g] / quant_mean[g - 1])) / diag::log(bin_center[g] / bin_center[g - 1]);
 				}
 			}
 		}
@@ -344,25 +413,29 @@ struct MG {
 		for (int g = 0; g < nGroups_; ++g) {
 			double alpha = alpha_quant[g] + 1.0;
 			if (alpha > 100.) {
-				kappa[g] = kappa_lower[g] * std::pow(radBoundaryRatios[g], kel.expo[g]);
+				diag::took(diag::ALPHA_GT_100);
+				kappa[g] = kappa_lower[g] * diag::pow(radBoundaryRatios[g], kel.expo[g]);
 				continue;
 			}
 			if (alpha < -100.) {
+				diag::took(diag::ALPHA_LT_M100);
 				kappa[g] = kappa_lower[g];
 				continue;
 			}
 			double part1 = 0.0;
 			if (std::abs(alpha) < 1e-8) {
-				part1 = std::log(radBoundaryRatios[g]);
+				diag::took(diag::ALPHA_NEAR_0);
+				part1 = diag::log(radBoundaryRatios[g]);
 			} else {
-				part1 = (std::pow(radBoundaryRatios[g], alpha) - 1.0) / alpha;
+				part1 = (diag::pow(radBoundaryRatios[g], alpha) - 1.0) / alpha;
 			}
 			alpha += alpha_kappa[g];
 			double part2 = 0.0;
 			if (std::abs(alpha) < 1e-8) {
-				part2 = std::log(radBoundaryRatios[g]);
+				diag::took(diag::ALPHA_NEAR_0);
+				part2 = diag::log(radBoundaryRatios[g]);
 			} else {
-				part2 = (std::pow(radBoundaryRatios[g], alpha) - 1.0) / alpha;
+				part2 = (diag::pow(radBoundaryRatios[g], alpha) - 1.0) / alpha;
 			}
 			kappa[g] = kappa_lower[g] / part1 * part2;
 		}
@@ -381,9 +454,9 @@ struct MG {
 		if (x <= 1.0e-10) {
 			planck_integral = x * x - x * x * x / 2.;
 		} else {
-			planck_integral = std::pow(x, 3) / (std::exp(x) - 1.0);
+			planck_integral = diag::pow(x, 3) / (diag::exp(x) - 1.0);
 		}
-		return coeff / (std::pow(planck::PI, 4) / 15.0) * (rs.rt.radiation_constant * std::pow(T, 4)) * planck_integral;
+		return coeff / (diag::pow(planck::PI, 4) / 15.0) * (rs.rt.radiation_constant * diag::pow(T, 4)) * planck_integral;
 	}
 
 	// :1328-1352
@@ -396,6 +469,7 @@ struct MG {
 				    1. / 3. * (kappa_slope[g] * kappaEVec[g] * fourPiBoverC[g] - delta_nu_kappa_B_at_edge[g]);
 			auto const denom = 4. / 3. * fourPiBoverC[g] - 1. / 3. * delta_nu_B_at_edge[g];
 			if (denom <= 0.0) {
+				diag::took(diag::DENOM_LE_0);
 				kappaF[g] = 0.0;
 			} else {
 				kappaF[g] /= denom;
@@ -409,7 +483,7 @@ struct MG {
 	{
 		VA kappa_center(nGroups_);
 		for (int g = 0; g < nGroups_; ++g) {
-			kappa_center[g] = kel.lower[g] * std::pow(rad_boundaries[g + 1] / rad_boundaries[g], 0.5 * kel.expo[g]);
+			kappa_center[g] = kel.lower[g] * diag::pow(rad_boundaries[g + 1] / rad_boundaries[g], 0.5 * kel.expo[g]);
 		}
 		return kappa_center;
 	}
@@ -449,6 +523,7 @@ struct MG {
 				result.alpha_E = ComputeRadQuantityExponents(Erad, rad_boundaries);
 				result.alpha_P = ComputeRadQuantityExponents(fourPiBoverC, rad_boundaries);
 			} else {
+				diag::took(diag::SLOPES_FROZEN);
 				result.alpha_E = alpha_E;
 				result.alpha_P = alpha_P;
 			}
@@ -477,7 +552,7 @@ struct MG {
 			auto const B_L = PlanckFunction(nu_L, T);
 			auto const B_R = PlanckFunction(nu_R, T);
 			auto const kappa_L = kappa_expo_and_lower_value.lower[g];
-			auto const kappa_R = kappa_L * std::pow(nu_R / nu_L, kappa_expo_and_lower_value.expo[g]);
+			auto const kappa_R = kappa_L * diag::pow(nu_R / nu_L, kappa_expo_and_lower_value.expo[g]);
 			opacity_terms.delta_nu_kappa_B_at_edge[g] = nu_R * kappa_R * B_R - nu_L * kappa_L * B_L;
 			delta_nu_B_at_edge[g] = nu_R * B_R - nu_L * B_L;
 		}
@@ -514,6 +589,7 @@ struct MG {
 		result.Jgg = VA(nGroups_);
 		for (int g = 0; g < nGroups_; ++g) {
 			if (tau[g] <= 0.0) {
+				diag::took(diag::ZERO_TAU);
 				result.Jgg[g] = -std::numeric_limits<double>::infinity();
 			} else {
 				result.Jgg[g] = -1.0 * kappaPoverE[g] / tau[g] - 1.0;
@@ -619,6 +695,7 @@ struct MG {
 
 			const double T_rad = std::sqrt(std::sqrt(sum(EradVec_guess) / rs.rt.radiation_constant));
 			if (enable_dE_constrain && delta_x / c_v > std::max(T_gas, T_rad)) {
+				diag::took(diag::DE_CONSTRAIN);
 				Egas_guess = rs.eos.ComputeEintFromTgas(rho, T_rad);
 			} else {
 				Egas_guess += delta_x;
@@ -709,6 +786,7 @@ struct MG {
 		result.Jgg = VA(nGroups_);
 		for (int g = 0; g < nGroups_; ++g) {
 			if (tau[g] <= 0.0) {
+				diag::took(diag::ZERO_TAU);
 				result.Jgg[g] = -std::numeric_limits<double>::infinity();
 			} else {
 				result.Jgg[g] = -1.0 * kappaPoverE[g] / tau[g] - 1.0;
@@ -742,6 +820,7 @@ struct MG {
 		auto d_Eg_d_Rg = -1.0 * kappaPoverE;
 		for (int g = 0; g < nGroups_; ++g) {
 			if (tau[g] <= 0.0) {
+				diag::took(diag::ZERO_TAU);
 				d_Eg_d_Rg[g] = -LARGE;
 			} else {
 				d_Eg_d_Rg[g] /= tau[g];
@@ -808,6 +887,7 @@ struct MG {
 		result.Jgg = VA(nGroups_);
 		for (int g = 0; g < nGroups_; ++g) {
 			if (tau[g] <= 0.0) {
+				diag::took(diag::ZERO_TAU);
 				result.Jgg[g] = -std::numeric_limits<double>::infinity();
 			} else {
 				result.Jgg[g] = -1.0 * kappaPoverE[g] / tau[g] - 1.0;
@@ -833,11 +913,13 @@ struct MG {
 		const double T_gas0 = rs.eos.ComputeTgasFromEint(rho, Egas0);
 		T_d0 = ComputeDustTemperatureBateKeto(T_gas0, T_gas0, rho, Erad0Vec, coeff_n, dt, NAN, 0, rad_boundaries);
 		if (T_d0 < 0.0) {
+			diag::took(diag::NEGATIVE_DUST_T);
 			p_iteration_failure_counter[1] += 1;
 		}
 		const double max_Gamma_gd = coeff_n * std::max(std::sqrt(T_gas0) * T_gas0, std::sqrt(T_d0) * T_d0);
 		if (cscale * max_Gamma_gd < rs.rt.gas_dust_coupling_threshold * Egas0) {
 			dust_model = 2;
+			diag::took(diag::DECOUPLED);
 			lambda_gd_times_dt = coeff_n * std::sqrt(T_gas0) * (T_gas0 - T_d0);
 		}
 		double Etot0 = NAN;
@@ -890,6 +972,7 @@ struct MG {
 				}
 			}
 			if (T_d < 0.0) {
+				diag::took(diag::NEGATIVE_DUST_T);
 				p_iteration_failure_counter[1] += 1;
 			}
 
@@ -960,6 +1043,7 @@ struct MG {
 			} else {
 				const double T_rad = std::sqrt(std::sqrt(sum(EradVec_guess) / rs.rt.radiation_constant));
 				if (enable_dE_constrain && delta_x / c_v > std::max(T_gas, T_rad)) {
+					diag::took(diag::DE_CONSTRAIN);
 					Egas_guess = rs.eos.ComputeEintFromTgas(rho, T_rad);
 				} else {
 					Egas_guess += delta_x;

@@ -1042,6 +1042,26 @@ QK_DEV void radSourceCellMG(Rad const &r, M &m, Eos const &eos, double U[RAD0 + 
 				const double F_coeff = chat * rho * en.ot.kappaF[g] * dt;
 				double Tedd[3][3];
 				eddingtonTensor(r, fx, fy, fz, Tedd);
+				// A group that holds no energy after the solve (none before, no thermal energy at this temperature) has the reduced flux
+				// F / (c * 0): per component NaN for F = 0 and +-inf otherwise in the reference, NaN either way from divBy.  In the
+				// reference f is then NaN (any component without flux) or inf.  Levermore's closure: clamp(NaN, 0., 1.) keeps the NaN, and
+				// f = inf makes the unit vector inf / inf: the tensor is NaN either way, and with it the pressure term, the group's flux and
+				// the gas momentum.  chi = 1/3 has no clamp: f = NaN fails `f > 0`, n = 0, and the tensor is the finite one of f = 0; only
+				// f = inf (all three components with flux) gives NaN.  clampd (v_max / v_min, qk_device.hpp) drops a NaN in its first
+				// argument and the select in eddingtonTensor discards the NaN quotients, so the reference's non-number is restored here.
+				// The test below is meant for E_g == 0.  f_sum is also NaN where E_g != 0 and two components overflow to infinities of
+				// opposite sign; with chi = 1/3 the all-components-with-flux test then stands in for `f = inf`, which is the same condition
+				// only for E_g == 0 (a reduced flux that overflows needs |F| > 1e308 c E_g: no state the scheme produces).
+				const double f_sum = (fx + fy) + fz;
+				if (f_sum != f_sum && (r.eddington_model != 1 || (Frad_t0[0] != 0. && Frad_t0[1] != 0. && Frad_t0[2] != 0.))) {
+#pragma unroll
+					for (int n = 0; n < 3; ++n) {
+#pragma unroll
+						for (int z = 0; z < 3; ++z) {
+							Tedd[n][z] = f_sum;
+						}
+					}
+				}
 #pragma unroll
 				for (int n = 0; n < 3; ++n) {
 					double Planck_term = en.ot.kappaP[g] * fourPiBoverC[g] - 1.0 / 3.0 * en.ot.delta_nu_kappa_B_at_edge[g]; // include_delta_B
