@@ -342,7 +342,26 @@ typedef struct qk_rad_traits {
 /* State layout: Physics_Indices (reference src/physics_info.hpp:20-47): comps 0..5 hydro, 6 + 4 g .. 9 + 4 g = (E_r, F_x, F_y, F_z) of group g.
  * The operators below act on all groups (primVar / flux arrays carry 4 * ngroups components, group-major like the state). */
 
-/* ConservedToPrimitive(cons, primVar, indexRange = valid grown by nghost); primVar has 4 * ngroups comps   reference src/radiation/radiation_system.hpp:589-614 */
+/* The five transport entries — ConservedToPrimitive, ComputeFluxes, computeRadiationFluxes, PredictStep / AddFluxesRK2 and stage_fused — return the
+ * reference's bits, non-numbers included (tests/test_rad_transport_cells_gpu.py, measured on an MI355X):
+ *   - A cell with E = 0 (what the state repair leaves of a negative energy when Erad_floor = 0) has the reduced flux F / (c 0): +-inf where F != 0,
+ *     NaN where F = 0; ConservedToPrimitive returns exactly these.  A face of such a cell takes the first-order
+ *     fallback: its energy flux is finite, its three momentum fluxes are NaN (Levermore's closure: clamp(NaN, 0., 1.) keeps the NaN; chi = 1/3: NaN
+ *     only where all three components of F are non-zero).  The faces whose reconstruction stencil holds the cell are NaN in the components in which
+ *     the reference's limiters (std::min, std::minmax, clamp) hand the NaN on, and the update stores NaN in the cell and in those neighbours.  The
+ *     reference counts such a run as failed (AMREX_ASSERT(!isnan(F))); nothing finite takes the place of its non-numbers.
+ *   - Range: every bit of the flux and of the primitives equals the reference's on the ladder E = 1e-300 ... 1e300 with c = 1024 (c E from 1e-297 to
+ *     1e303; relied on and asserted: c E of both cells in [2^-996, 2^1004], the range of the shared reciprocal) and on the ladder |f| = 1e-200 ... 1
+ *     (f^2 subnormal or zero at its lower end): no E and no |f| was found at which the transport leaves bit parity.
+ *   - One difference is left, by decision: where two of the three cell values PPM's std::minmax compares are zeros of OPPOSITE sign, the reference
+ *     returns one by position and v_min_f64 / v_max_f64 one by sign, and an exactly-zero flux may carry the other sign (csrc/qk_device.hpp, smin / smax;
+ *     6 of 459200 flux and state entries of a 40^3 level whose cells without flux hold -0).  The REF forms of the limiters give the reference's zero, but
+ *     no flag marks such a stencil: finding it takes a sign test on three values of every component of every cell, on top of the 5 ... 8 % the
+ *     per-cell flag of a non-number already costs the fused stage (profiles/rad_transport_pins/ab_timing.txt) — for a zero whose sign changes no
+ *     later value.
+ *   - With several photon groups the validity test is the whole cell's and the repair then amends every group (a valid one below its floor is lifted),
+ *     on the fused route as on the separate one (:626-665).
+ * ConservedToPrimitive(cons, primVar, indexRange = valid grown by nghost); primVar has 4 * ngroups comps   reference src/radiation/radiation_system.hpp:589-614 */
 int qk_rad_ConservedToPrimitive(qk_level *lev, qk_stream s, const qk_rad_traits *rt, const qk_array4 *cons, qk_array4 *primVar, int nghost);
 /* RadSystem::ComputeCellOpticalDepth<DIR> for every face, and what the use_wavespeed_correction branch of ComputeFluxes makes of it: eps[d] (face-centred
  * in d, no ghost cells, ngroups components) receives epsilon = min(1, 1 / tau_cell) on the faces whose i + j + k is even and 1 on the others, tau_cell the
@@ -367,7 +386,8 @@ int qk_rad_computeRadiationFluxes(qk_level *lev, qk_stream s, const qk_rad_trait
  * kernels (X, Y accumulate into `acc`: 4 components per cell, no ghost cells; Z finishes the update and repairs invalid states) — the state
  * equals the separate calls' in every bit.  U_new may be the arrays of U_in.  flux_out: NULL or three face-centred arrays that receive the
  * fluxes (flux registers).  3-D levels; with several photon groups (acc and the face arrays hold 4 components per group) one set of sweeps per group —
- * the groups are transported independently.  1-D / 2-D levels: QK_ERR_UNSUPPORTED (the separate calls serve them).
+ * the groups are transported independently, each stored unrepaired, and one more pass over the cells gives the whole cell's verdict and repairs every
+ * group of an invalid cell (one group: the Z sweep repairs).  1-D / 2-D levels: QK_ERR_UNSUPPORTED (the separate calls serve them).
  *                                                    reference src/QuokkaSimulation.hpp:1726-1882, src/radiation/radiation_system.hpp:667-775 */
 int qk_rad_stage_fused(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int reconstruction_order, int stage, const qk_array4 *U_in, const qk_array4 *U0,
 		       qk_array4 *U_new, qk_array4 *acc, qk_array4 *const flux_out[3], double dt, const double dx[3],

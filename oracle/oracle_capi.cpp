@@ -846,4 +846,127 @@ void orc_rad_mg_source_cells(orc_rad_mg_cell_traits const *t, long n, double *U,
 	}
 }
 
+// ------------------------------------------------------------------ the radiation transport operators, face by face and stage by stage
+// Of orc_rad_cell_traits these read c_light, c_hat, Erad_floor and eddington_model.
+static auto transportSystem(orc_rad_cell_traits const *t, int ngroups, int ndim, int nstart) -> RadSystem
+{
+	RadSystem rs;
+	rs.rt.c_light = t->c_light;
+	rs.rt.c_hat = t->c_hat;
+	rs.rt.Erad_floor = t->Erad_floor;
+	rs.rt.eddington_model = t->eddington_model;
+	rs.rt.nGroups = ngroups;
+	rs.nstartHyperbolic_ = nstart;
+	rs.ndim = ndim;
+	return rs;
+}
+
+// ConservedToPrimitive (radiation_system.hpp:589-614) on n cells of one group: cons[4][n] -> prim[4][n], component outermost
+void orc_rad_cons_to_prim(orc_rad_cell_traits const *t, long n, double const *cons, double *prim)
+{
+	RadSystem const rs = transportSystem(t, 1, 1, 0);
+	Box row;
+	row.hi[0] = static_cast<int>(n) - 1;
+	rs.ConservedToPrimitive(Array4<const double>(cons, row, 4), Array4<double>(prim, row, 4), row);
+}
+
+// ComputeFluxes<dir[f]> (radiation_system.hpp:985-1139) on each of n faces as a box of one face: pL / pR the reconstructed primitive states,
+// consL / consR the conserved states of the two cells, eps the factor S_corr of the face (1: no wavespeed correction); all [4][n], component
+// outermost.  F[4][n] receives the flux, mask[n] tdiag::Face.
+void orc_rad_face_fluxes(orc_rad_cell_traits const *t, long n, int const *dir, double const *pL, double const *pR, double const *consL, double const *consR,
+			 double const *eps, double *F, int *mask)
+{
+	g_spacedim = 3;
+	RadSystem const rs = transportSystem(t, 1, 3, 0);
+	_Pragma("omp parallel for schedule(static)")
+	for (long f = 0; f < n; ++f) {
+		int const d = dir[f];
+		Box face; // lo = hi = (0, 0, 0): the face between cells -1 and 0 along d
+		Box cells;
+		cells.lo[d] = -1;
+		double l[4], r[4], U[8], e = eps[f], flux[4], diffusive[4];
+		for (int c = 0; c < 4; ++c) {
+			l[c] = pL[c * n + f];
+			r[c] = pR[c * n + f];
+			U[2 * c] = consL[c * n + f]; // (two cells along d, component outermost)
+			U[2 * c + 1] = consR[c * n + f];
+		}
+		int m = 0;
+		Array4<const double> const epsA(&e, face, 1);
+		Array4<int> const maskA(&m, face, 1);
+		rs.ComputeFluxes(d, Array4<double>(flux, face, 4), Array4<double>(diffusive, face, 4), Array4<const double>(l, face, 4), Array4<const double>(r, face, 4),
+				 face, Array4<const double>(U, cells, 4), nullptr, false, &epsA, &maskA);
+		for (int c = 0; c < 4; ++c) {
+			F[c * n + f] = flux[c];
+		}
+		mask[f] = m;
+	}
+}
+
+// One transport stage of one box on arrays the caller owns and has ghost-filled (nghost cells in the first ndim directions, 6 + 4 ngroups
+// components): computeRadiationFluxes (QuokkaSimulation.hpp:1884-1961: ConservedToPrimitive, the reconstruction of `order`, ComputeFluxes per
+// direction) of U_in, then PredictStep(U0 -> U_new) (stage 1) or AddFluxesRK2(U_new; U0, U1 = U_in; the old-state fluxes, of weight 0.5 - IMEX_a32
+// = 0, are those of U0) (stage 2).  eps[d]: NULL or S_corr per face and group; flux[d] / fmask[d]: the face arrays of direction d (4 ngroups /
+// ngroups components), cmask: the valid box, ngroups components.  U_new: only the radiation components of the valid cells are written.
+void orc_rad_transport_stage(orc_rad_cell_traits const *t, int ngroups, int ndim, int order, int stage, double const *U_in, double const *U0, double *U_new,
+			     int const vlo[3], int const vhi[3], int nghost, double dt, double const dx[3], double const *const eps[3], double *const flux[3],
+			     int *const fmask[3], int *cmask)
+{
+	g_spacedim = ndim;
+	RadSystem const rs = transportSystem(t, ngroups, ndim, 6);
+	int const nvars = rs.nRadComps(), ncomp = 6 + nvars;
+	Box const indexRange = mkbox(vlo, vhi);
+	Box const ghostRange = grow(indexRange, nghost, ndim);
+	auto fluxesOf = [&](double const *U, bool record) {
+		Array4<const double> const consVar(U, ghostRange, ncomp);
+		std::array<Fab<double>, 3> out;
+		for (int dir = 0; dir < ndim; ++dir) {
+			Box const reconstructRange = grow(indexRange, 1, ndim);
+			Box const x1ReconstructRange = faceBox(reconstructRange, dir);
+			Fab<double> primVar(ghostRange, nvars);
+			Fab<double> x1LeftState(x1ReconstructRange, nvars);
+			Fab<double> x1RightState(x1ReconstructRange, nvars);
+			rs.ConservedToPrimitive(consVar, primVar.array(), ghostRange);
+			if (order == 3) {
+				ReconstructStatesPPM(dir, primVar.const_array(), x1LeftState.array(), x1RightState.array(), reconstructRange, nvars);
+			} else if (order == 2) {
+				ReconstructStatesPLM(dir, lim_MC, primVar.const_array(), x1LeftState.array(), x1RightState.array(), x1ReconstructRange, nvars);
+			} else {
+				ReconstructStatesConstant(dir, primVar.const_array(), x1LeftState.array(), x1RightState.array(), x1ReconstructRange, nvars);
+			}
+			Box const x1FluxRange = faceBox(indexRange, dir);
+			out[dir] = Fab<double>(x1FluxRange, nvars);
+			Fab<double> diffusive(x1FluxRange, nvars);
+			Fab<int> took(x1FluxRange, ngroups);
+			Array4<const double> const epsA((eps != nullptr && eps[dir] != nullptr) ? eps[dir] : nullptr, x1FluxRange, ngroups);
+			Array4<int> const tookA = took.array();
+			rs.ComputeFluxes(dir, out[dir].array(), diffusive.array(), x1LeftState.const_array(), x1RightState.const_array(), x1FluxRange, consVar, nullptr,
+					 false, (epsA.p != nullptr) ? &epsA : nullptr, &tookA);
+			if (record) {
+				std::copy(out[dir].d.begin(), out[dir].d.end(), flux[dir]);
+				std::copy(took.d.begin(), took.d.end(), fmask[dir]);
+			}
+		}
+		return out;
+	};
+	auto const fl = fluxesOf(U_in, true);
+	std::array<Array4<const double>, 3> f{};
+	for (int d = 0; d < ndim; ++d) {
+		f[d] = fl[d].const_array();
+	}
+	Array4<int> const cellMask(cmask, indexRange, ngroups);
+	Array4<double> const out(U_new, ghostRange, ncomp);
+	if (stage == 1) {
+		rs.PredictStep(Array4<const double>(U0, ghostRange, ncomp), out, f, dt, dx, indexRange, &cellMask);
+	} else {
+		auto const flOld = fluxesOf(U0, false);
+		std::array<Array4<const double>, 3> f0{};
+		for (int d = 0; d < ndim; ++d) {
+			f0[d] = flOld[d].const_array();
+		}
+		// (U_new may be the array of U_in, as in the driver: AddFluxesRK2 reads U1 and writes U_new at the same cell only)
+		rs.AddFluxesRK2(out, Array4<const double>(U0, ghostRange, ncomp), Array4<const double>(U_in, ghostRange, ncomp), f0, f, dt, dx, indexRange, &cellMask);
+	}
+}
+
 } // extern "C"

@@ -87,6 +87,13 @@ MG_BRANCHES = ("zero_tau", "dE_constrain", "denom_le_0", "alpha_gt_100", "alpha_
                "slopes_frozen", "floor_clamp", "x_ge_100", "below_table", "decoupled", "negative_dust_T")
 MG_BRANCH_BIT = {name: 1 << i for i, name in enumerate(MG_BRANCHES)}
 
+# the bits orc_rad_face_fluxes / orc_rad_transport_stage record per face and per cell (oracle/radiation.hpp, tdiag::Face / tdiag::Cell)
+RAD_FACE_BRANCHES = ("fallback", "erad_L_le_0", "erad_R_le_0", "f_L_ge_1", "f_R_ge_1", "clamp_L", "clamp_R", "no_dir_L", "no_dir_R", "S_floor_L", "S_floor_R",
+                     "nonfinite")
+RAD_FACE_BIT = {name: 1 << i for i, name in enumerate(RAD_FACE_BRANCHES)}
+RAD_CELL_BRANCHES = ("invalid_E", "invalid_f", "f_nan", "lifted", "rescaled", "by_other")
+RAD_CELL_BIT = {name: 1 << i for i, name in enumerate(RAD_CELL_BRANCHES)}
+
 
 class SimConfig(C.Structure):
     _fields_ = [
@@ -231,6 +238,71 @@ class Oracle:
             self.set_libm_jitter(0, 0)
         keys = ("solves", "newton", "newton_max", "fail_newton", "fail_outer", "fail_dust", "decoupled", "mask")
         return U, dict(zip(keys, rec)), [int(v) for v in tot]
+
+    # ---------------------------------------------------------------- the radiation transport operators, face by face and stage by stage
+    def rad_cons_to_prim(self, t: RadCellTraits, cons: np.ndarray) -> np.ndarray:
+        """ConservedToPrimitive of one photon group on cons[4, n] = (E, Fx, Fy, Fz): prim[4, n] = (E, fx, fy, fz)"""
+        cons = np.ascontiguousarray(cons, dtype=np.float64)
+        assert cons.ndim == 2 and cons.shape[0] == 4
+        prim = np.empty_like(cons)
+        f = self.lib.orc_rad_cons_to_prim
+        f.argtypes, f.restype = [C.POINTER(RadCellTraits), C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double)], None
+        f(C.byref(t), cons.shape[1], _dp(cons), _dp(prim))
+        return prim
+
+    def rad_face_fluxes(self, t: RadCellTraits, direction, pL, pR, consL, consR, eps=None):
+        """ComputeFluxes on n faces, each a box of its own: direction[n] (0..2), pL / pR / consL / consR [4, n], eps[n] (None: 1, no wavespeed
+        correction).  Returns (F[4, n], mask[n]) with the bits of RAD_FACE_BIT"""
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (pL, pR, consL, consR)]
+        n = a[0].shape[1]
+        assert all(v.shape == (4, n) for v in a)
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(direction, dtype=np.int32), (n,)))
+        e = np.ones(n) if eps is None else np.ascontiguousarray(eps, dtype=np.float64)
+        assert e.shape == (n,) and d.min() >= 0 and d.max() <= 2
+        F, mask = np.empty((4, n)), np.zeros(n, dtype=np.int32)
+        f = self.lib.orc_rad_face_fluxes
+        DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        f.argtypes, f.restype = [C.POINTER(RadCellTraits), C.c_long, IP, DP, DP, DP, DP, DP, DP, IP], None
+        self.lib.orc_set_num_threads(int(max(1, min(usable_cores(), n // 4096))))
+        f(C.byref(t), n, d.ctypes.data_as(IP), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), _dp(e), _dp(F), mask.ctypes.data_as(IP))
+        return F, mask
+
+    def rad_transport_stage(self, t: RadCellTraits, ngroups: int, ndim: int, order: int, stage: int, U_in: np.ndarray, U0: np.ndarray, vlo, vhi, dt: float, dx,
+                            eps=None, nghost: int = 4):
+        """One transport stage of one box on ghost-filled arrays (6 + 4 ngroups, nz, ny, nx) that the caller owns: computeRadiationFluxes(U_in) and
+        PredictStep(U0) (stage 1) or AddFluxesRK2(U0, U1 = U_in) (stage 2).  eps: None or one array (ngroups, faces...) per direction.  Returns
+        (U_new — a copy of U_in with the radiation components of the valid cells replaced —, [flux_d (4 ngroups, faces...)], [face mask_d (ngroups,
+        faces...), RAD_FACE_BIT], cell mask (ngroups, valid cells...), RAD_CELL_BIT)"""
+        U_in = np.ascontiguousarray(U_in, dtype=np.float64)
+        U0 = np.ascontiguousarray(U0, dtype=np.float64)
+        nv = [int(vhi[d] - vlo[d] + 1) for d in range(3)]
+        shape = (6 + 4 * ngroups,) + tuple(nv[d] + (2 * nghost if d < ndim else 0) for d in (2, 1, 0))
+        assert U_in.shape == shape and U0.shape == shape, (U_in.shape, U0.shape, shape)
+        U_new = U_in.copy()
+        DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        flux, fmask, epsp = [], [], (DP * 3)()
+        fp, mp = (DP * 3)(), (IP * 3)()
+        keep = []
+        for d in range(ndim):
+            n = list(nv)
+            n[d] += 1
+            fs = (n[2], n[1], n[0])
+            flux.append(np.empty((4 * ngroups,) + fs))
+            fmask.append(np.zeros((ngroups,) + fs, dtype=np.int32))
+            fp[d], mp[d] = _dp(flux[d]), fmask[d].ctypes.data_as(IP)
+            if eps is not None and eps[d] is not None:
+                e = np.ascontiguousarray(eps[d], dtype=np.float64)
+                assert e.shape == (ngroups,) + fs
+                keep.append(e)
+                epsp[d] = _dp(e)
+        cmask = np.zeros((ngroups, nv[2], nv[1], nv[0]), dtype=np.int32)
+        f = self.lib.orc_rad_transport_stage
+        f.argtypes = [C.POINTER(RadCellTraits), C.c_int, C.c_int, C.c_int, C.c_int, DP, DP, DP, _I3, _I3, C.c_int, C.c_double, C.c_double * 3, DP * 3, DP * 3,
+                      IP * 3, IP]
+        f.restype = None
+        f(C.byref(t), int(ngroups), int(ndim), int(order), int(stage), _dp(U_in), _dp(U0), _dp(U_new), _i3(vlo), _i3(vhi), int(nghost), float(dt),
+          (C.c_double * 3)(*[float(x) for x in dx]), epsp, fp, mp, cmask.ctypes.data_as(IP))
+        return U_new, flux, fmask, cmask
 
     # ---------------------------------------------------------------- multigroup helper functions
     def planck_integral(self, x: float) -> float:

@@ -68,6 +68,34 @@ struct RadTraits {
 	int opacity_model = single_group;
 };
 
+// What the transport operators record for the tests, one word per face / cell and photon group (tests/rad_transport_reference.py): which
+// branch of ComputeFluxes a face took, what isStateValid / amendRadState did to a cell.  Recording changes no value.
+namespace tdiag
+{
+enum Face : int {
+	FALLBACK = 1 << 0,	// :1054 first-order fallback taken
+	ERAD_L_LE_0 = 1 << 1,	// its four conditions
+	ERAD_R_LE_0 = 1 << 2,
+	F_L_GE_1 = 1 << 3,
+	F_R_GE_1 = 1 << 4,
+	CLAMP_L = 1 << 5,	// f > 1 after the fallback: ComputeEddingtonFactor clamps it
+	CLAMP_R = 1 << 6,
+	NO_DIR_L = 1 << 7,	// (f > 0.) false in ComputeEddingtonTensor: n = 0
+	NO_DIR_R = 1 << 8,
+	S_FLOOR_L = 1 << 9,	// std::max(0.1, sqrt(Tnormal)) returned 0.1
+	S_FLOOR_R = 1 << 10,
+	NONFINITE = 1 << 11	// a component of the flux is NaN or infinite
+};
+enum Cell : int {
+	INVALID_E = 1 << 0,	// this group: !(E_r > 0.)
+	INVALID_F = 1 << 1,	// this group: f > 1
+	F_NAN = 1 << 2,		// this group: f is NaN
+	LIFTED = 1 << 3,	// amendRadState raised the energy to the floor
+	RESCALED = 1 << 4,	// amendRadState rescaled the flux
+	BY_OTHER = 1 << 5	// lifted or rescaled although this group was valid: another group of the cell was not
+};
+} // namespace tdiag
+
 struct RadSystem {
 	RadTraits rt;
 	EOS eos;
@@ -302,6 +330,42 @@ struct RadSystem {
 		return isValid;
 	}
 
+	// what isStateValid and amendRadState (would) do to every group of `cons`: tdiag::Cell per group, the same comparisons restated
+	void recordCell(RadCons const &cons, int *mask) const
+	{
+		bool cellValid = true;
+		bool groupValid[kMaxGroups];
+		for (int g = 0; g < nGroups_(); ++g) {
+			const auto E_r = cons[0 + kNumRadVars * g];
+			const auto Fx = cons[1 + kNumRadVars * g];
+			const auto Fy = cons[2 + kNumRadVars * g];
+			const auto Fz = cons[3 + kNumRadVars * g];
+			const auto f = std::sqrt(Fx * Fx + Fy * Fy + Fz * Fz) / (rt.c_light * E_r);
+			groupValid[g] = (E_r > 0.) && (f <= 1.);
+			cellValid = cellValid && groupValid[g];
+			mask[g] = (!(E_r > 0.) ? tdiag::INVALID_E : 0) | ((f > 1.) ? tdiag::INVALID_F : 0) | ((f != f) ? tdiag::F_NAN : 0);
+		}
+		if (cellValid) {
+			return;
+		}
+		for (int g = 0; g < nGroups_(); ++g) {
+			auto E_r = cons[0 + kNumRadVars * g];
+			if (E_r < Erad_floor_()) {
+				E_r = Erad_floor_();
+				mask[g] |= tdiag::LIFTED;
+			}
+			const auto Fx = cons[1 + kNumRadVars * g];
+			const auto Fy = cons[2 + kNumRadVars * g];
+			const auto Fz = cons[3 + kNumRadVars * g];
+			if (Fx * Fx + Fy * Fy + Fz * Fz > rt.c_light * rt.c_light * E_r * E_r) {
+				mask[g] |= tdiag::RESCALED;
+			}
+			if (groupValid[g] && (mask[g] & (tdiag::LIFTED | tdiag::RESCALED)) != 0) {
+				mask[g] |= tdiag::BY_OTHER;
+			}
+		}
+	}
+
 	// :646-665
 	void amendRadState(RadCons &cons) const
 	{
@@ -376,8 +440,11 @@ struct RadSystem {
 	// :985-1139; use_wavespeed_correction (QuokkaSimulation.hpp:133, default false) with the cell widths it needs
 	void ComputeFluxes(int dir, Array4<double> const &x1Flux_in, Array4<double> const &x1FluxDiffusive_in, Array4<const double> const &x1LeftState_in,
 			   Array4<const double> const &x1RightState_in, Box const &indexRange, Array4<const double> const &consVar_in, double const *dx = nullptr,
-			   bool const use_wavespeed_correction = false) const
+			   bool const use_wavespeed_correction = false, Array4<const double> const *epsFace = nullptr,
+			   Array4<int> const *faceMask = nullptr) const
 	{
+		// epsFace: S_corr of every face and group given by the caller (indexed like the flux array) instead of ComputeCellOpticalDepth;
+		// faceMask: receives tdiag::Face per face and group
 		View<const double> x1LeftState(x1LeftState_in, dir);
 		View<const double> x1RightState(x1RightState_in, dir);
 		View<double> x1Flux(x1Flux_in, dir);
@@ -411,6 +478,8 @@ struct RadSystem {
 
 						double f_L = std::sqrt(fx_L * fx_L + fy_L * fy_L + fz_L * fz_L);
 						double f_R = std::sqrt(fx_R * fx_R + fy_R * fy_R + fz_R * fz_R);
+						int took = ((erad_L <= 0.) ? tdiag::ERAD_L_LE_0 : 0) | ((erad_R <= 0.) ? tdiag::ERAD_R_LE_0 : 0) |
+							   ((f_L >= 1.) ? tdiag::F_L_GE_1 : 0) | ((f_R >= 1.) ? tdiag::F_R_GE_1 : 0);
 
 						double Fx_L = fx_L * (c_light_ * erad_L);
 						double Fx_R = fx_R * (c_light_ * erad_R);
@@ -421,6 +490,7 @@ struct RadSystem {
 
 						// :1054-1079 first-order fallback
 						if ((erad_L <= 0.) || (erad_R <= 0.) || (f_L >= 1.) || (f_R >= 1.)) {
+							took |= tdiag::FALLBACK;
 							erad_L = consVar(i - 1, j, k, radEnergy_index() + pg);
 							erad_R = consVar(i, j, k, radEnergy_index() + pg);
 							Fx_L = consVar(i - 1, j, k, x1RadFlux_index() + pg);
@@ -442,6 +512,7 @@ struct RadSystem {
 						auto [F_L, S_L] = ComputeRadPressure(dir, erad_L, Fx_L, Fy_L, Fz_L, fx_L, fy_L, fz_L);
 						S_L *= -1.;
 						auto [F_R, S_R] = ComputeRadPressure(dir, erad_R, Fx_R, Fy_R, Fz_R, fx_R, fy_R, fz_R);
+						took |= ((S_L == -0.1) ? tdiag::S_FLOOR_L : 0) | ((S_R == 0.1) ? tdiag::S_FLOOR_R : 0);
 
 						// :1087-1094
 						F_L[0] *= c_hat_ / c_light_;
@@ -463,6 +534,11 @@ struct RadSystem {
 								epsilon = {S_corr, 1.0, 1.0, 1.0};
 							}
 						}
+						if (epsFace != nullptr) {
+							epsilon = {(*epsFace)(i_in, j_in, k_in, g), 1.0, 1.0, 1.0};
+						}
+						took |= ((f_L > 1.) ? tdiag::CLAMP_L : 0) | ((f_R > 1.) ? tdiag::CLAMP_R : 0) | (!(f_L > 0.) ? tdiag::NO_DIR_L : 0) |
+							(!(f_R > 0.) ? tdiag::NO_DIR_R : 0);
 
 						// :1116-1117, :1130-1131
 						for (int n = 0; n < kNumRadVars; ++n) {
@@ -472,6 +548,10 @@ struct RadSystem {
 							    (S_R / (S_R - S_L)) * F_L[n] - (S_L / (S_R - S_L)) * F_R[n] + (S_R * S_L / (S_R - S_L)) * (U_R[n] - U_L[n]);
 							x1Flux(i, j, k, pg + n) = F;
 							x1FluxDiffusive(i, j, k, pg + n) = diffusiveF;
+							took |= std::isfinite(F) ? 0 : tdiag::NONFINITE;
+						}
+						if (faceMask != nullptr) {
+							(*faceMask)(i_in, j_in, k_in, g) = took;
 						}
 					}
 				}
@@ -481,7 +561,7 @@ struct RadSystem {
 
 	// :667-710
 	void PredictStep(Array4<const double> const &consVarOld, Array4<double> const &consVarNew, std::array<Array4<const double>, 3> const &fluxArray,
-			 const double dt, double const dx_in[3], Box const &indexRange) const
+			 const double dt, double const dx_in[3], Box const &indexRange, Array4<int> const *cellMask = nullptr) const
 	{
 		for (int k = indexRange.lo[2]; k <= indexRange.hi[2]; ++k) {
 			for (int j = indexRange.lo[1]; j <= indexRange.hi[1]; ++j) {
@@ -497,6 +577,13 @@ struct RadSystem {
 						}
 						cons[n] = consVarOld(i, j, k, nstartHyperbolic_ + n) + d;
 					}
+					if (cellMask != nullptr) {
+						int m[kMaxGroups];
+						recordCell(cons, m);
+						for (int g = 0; g < nGroups_(); ++g) {
+							(*cellMask)(i, j, k, g) = m[g];
+						}
+					}
 					if (!isStateValid(cons)) {
 						amendRadState(cons);
 					}
@@ -511,7 +598,7 @@ struct RadSystem {
 	// :712-771
 	void AddFluxesRK2(Array4<double> const &U_new, Array4<const double> const &U0, Array4<const double> const &U1,
 			  std::array<Array4<const double>, 3> const &fluxArrayOld, std::array<Array4<const double>, 3> const &fluxArray, const double dt,
-			  double const dx_in[3], Box const &indexRange) const
+			  double const dx_in[3], Box const &indexRange, Array4<int> const *cellMask = nullptr) const
 	{
 		for (int k = indexRange.lo[2]; k <= indexRange.hi[2]; ++k) {
 			for (int j = indexRange.lo[1]; j <= indexRange.hi[1]; ++j) {
@@ -532,6 +619,13 @@ struct RadSystem {
 						}
 						// :758-759
 						cons_new[n] = (1.0 - IMEX_a32) * U_0 + IMEX_a32 * U_1 + ((0.5 - IMEX_a32) * (s0)) + (0.5 * (s1));
+					}
+					if (cellMask != nullptr) {
+						int m[kMaxGroups];
+						recordCell(cons_new, m);
+						for (int g = 0; g < nGroups_(); ++g) {
+							(*cellMask)(i, j, k, g) = m[g];
+						}
 					}
 					if (!isStateValid(cons_new)) {
 						amendRadState(cons_new);

@@ -290,29 +290,56 @@ QK_DEV void consToPrim(Eos const &eos, bool reconstruct_eint, const double U[NVA
 	}
 }
 
+// REF forms of the limiters below: std::min and math_impl.hpp's clamp as the reference's C++ evaluates them for ANY operands — a NaN is handed on where
+// smin / smax drop it, a tie between zeros goes by position.  The radiation transport asks for them on a stencil that holds a non-number
+// (qk_rad_ops.hip); REF = false, the default and what every hydro kernel instantiates, is the one-instruction form: same value for ordered operands.
+QK_DEV auto stdMin(double a, double b) -> double { return (b < a) ? b : a; }
+QK_DEV auto refClamp(double v, double lo, double hi) -> double { return (v < lo) ? lo : (hi < v) ? hi : v; }
 // hyperbolic_system.hpp:58-66
-QK_DEV auto MC(double a, double b) -> double { return 0.5 * (sgn(a) + sgn(b)) * smin(0.5 * fabs(a + b), smin(2.0 * fabs(a), 2.0 * fabs(b))); }
+template <bool REF = false> QK_DEV auto MC(double a, double b) -> double
+{
+	if constexpr (REF) {
+		return 0.5 * (sgn(a) + sgn(b)) * stdMin(0.5 * fabs(a + b), stdMin(2.0 * fabs(a), 2.0 * fabs(b)));
+	} else {
+		return 0.5 * (sgn(a) + sgn(b)) * smin(0.5 * fabs(a + b), smin(2.0 * fabs(a), 2.0 * fabs(b)));
+	}
+}
 QK_DEV auto minmod(double a, double b) -> double { return 0.5 * (sgn(a) + sgn(b)) * smin(fabs(a), fabs(b)); }
 
 // hyperbolic_system.hpp:337-433 : PPM edges of cell i from q(i-2..i+2).
 //   am -> rightState(i) (left edge of the cell), ap -> leftState(i+1) (right edge)
-QK_DEV void ppmEdges(double qm2, double qm1, double q0, double qp1, double qp2, double &am, double &ap)
+template <bool REF = false> QK_DEV void ppmEdges(double qm2, double qm1, double q0, double qp1, double qp2, double &am, double &ap)
 {
-	// std::minmax({q0, qm1, qp1})
-	const double lo = smin(smin(q0, qm1), qp1);
-	const double hi = smax(smax(q0, qm1), qp1);
+	// std::minmax({q0, qm1, qp1}); REF: libstdc++'s order of comparisons (the first of equal smallest, the last of equal largest)
+	double lo, hi;
+	if constexpr (REF) {
+		lo = hi = q0;
+		if (qm1 < q0) {
+			lo = qm1;
+		} else {
+			hi = qm1;
+		}
+		if (qp1 < lo) {
+			lo = qp1;
+		} else if (!(qp1 < hi)) {
+			hi = qp1;
+		}
+	} else {
+		lo = smin(smin(q0, qm1), qp1);
+		hi = smax(smax(q0, qm1), qp1);
+	}
 	const double coef_1 = (7. / 12.);
 	const double coef_2 = (-1. / 12.);
 	const double a_minus = (coef_1 * q0 + coef_2 * qp1) + (coef_1 * qm1 + coef_2 * qm2);
 	const double a_plus = (coef_1 * qp1 + coef_2 * qp2) + (coef_1 * q0 + coef_2 * qm1);
-	double new_a_minus = clampd(a_minus, lo, hi);
-	double new_a_plus = clampd(a_plus, lo, hi);
+	double new_a_minus = REF ? refClamp(a_minus, lo, hi) : clampd(a_minus, lo, hi);
+	double new_a_plus = REF ? refClamp(a_plus, lo, hi) : clampd(a_plus, lo, hi);
 	const double a = q0;
 	const double dq_minus = (a - new_a_minus);
 	const double dq_plus = (new_a_plus - a);
 	const double qa = dq_plus * dq_minus;
 	if (qa <= 0.0) {
-		const double dq0 = MC(qp1 - q0, q0 - qm1);
+		const double dq0 = MC<REF>(qp1 - q0, q0 - qm1);
 		new_a_minus = a - 0.5 * dq0;
 		new_a_plus = a + 0.5 * dq0;
 	} else {

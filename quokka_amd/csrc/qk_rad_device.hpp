@@ -74,14 +74,21 @@ struct Rad {
 	template <bool TDEP = false> QK_DEV auto kappaE(double rho, double T) const -> double { return kappaX<TDEP>(kappaE0, rho, T); }
 	template <bool TDEP = false> QK_DEV auto kappaF(double rho, double T) const -> double { return kappaX<TDEP>(kappaF0, rho, T); }
 	// the ComputeEddingtonFactor hook: 0 = Levermore closure (radiation_system.hpp:773-790, the default), 1 = Eddington approximation
-	QK_DEV auto eddingtonFactor(double f_in) const -> double
+	// KEEP_NAN: the reference's clamp(NaN, 0., 1.) keeps a NaN — the reduced flux of a cell with E = 0, F / (c 0) — and chi is NaN; clampd (v_max /
+	// v_min) drops it and chi would be that of f = 0.  The transport kernels ask for the reference's answer (a select on the result); the exchange
+	// kernels, whose call sites deal with an empty group themselves (qk_rad_mg_device.hpp), keep their code.
+	template <bool KEEP_NAN = false> QK_DEV auto eddingtonFactor(double f_in) const -> double
 	{
 		if (eddington_model == 1) {
 			return (1. / 3.);
 		}
 		const double f = clampd(f_in, 0., 1.);
 		const double f_fac = sqrtN(4.0 - 3.0 * (f * f));
-		return divN(3.0 + 4.0 * (f * f), 5.0 + 2.0 * f_fac);
+		const double chi = divN(3.0 + 4.0 * (f * f), 5.0 + 2.0 * f_fac);
+		if constexpr (KEEP_NAN) {
+			return (f_in != f_in) ? f_in : chi;
+		}
+		return chi;
 	}
 	// pow_mode 0 stands for the reference's std::pow(T, 4) / std::pow(T, 3), which glibc rounds correctly in all but a vanishing fraction of
 	// cases.  Evaluated here as compensated products (T^2 = hi + lo exactly by one fma; the product of the pair carried with its rounding
@@ -125,7 +132,7 @@ struct Rad {
 };
 
 // radiation_system.hpp:873-916: row `row` of the Eddington tensor, plus T[row][row] via Tn[row]
-QK_DEV void eddingtonTensor(Rad const &r, double fx, double fy, double fz, double T[3][3])
+template <bool KEEP_NAN = false> QK_DEV void eddingtonTensor(Rad const &r, double fx, double fy, double fz, double T[3][3])
 {
 	const double f = sqrtN(fx * fx + fy * fy + fz * fz);
 	const double fv[3] = {fx, fy, fz};
@@ -135,7 +142,7 @@ QK_DEV void eddingtonTensor(Rad const &r, double fx, double fy, double fz, doubl
 	for (int ii = 0; ii < 3; ++ii) {
 		n[ii] = (f > 0.) ? divBy(fv[ii], Rf) : 0.;
 	}
-	const double chi = r.eddingtonFactor(f);
+	const double chi = r.template eddingtonFactor<KEEP_NAN>(f);
 	const double Tdiag = (1.0 - chi) / 2.0;
 	const double Tf = (3.0 * chi - 1.0) / 2.0;
 #pragma unroll
@@ -185,8 +192,10 @@ QK_DEV void radFaceFlux(Rad const &r, const double pL[NRAD], const double pR[NRA
 		f_R = sqrtN(fx_R * fx_R + fy_R * fy_R + fz_R * fz_R);
 	}
 	double TL[3][3], TR[3][3];
-	eddingtonTensor(r, fx_L, fy_L, fz_L, TL);
-	eddingtonTensor(r, fx_R, fy_R, fz_R, TR);
+	// (a cell with E = 0 — what the state repair leaves of a negative energy when Erad_floor = 0 — has f = NaN here: the reference's tensor, and with
+	// it the momentum fluxes of the face, are NaN, which marks the run as failed; a finite flux in their place would hide that)
+	eddingtonTensor<true>(r, fx_L, fy_L, fz_L, TL);
+	eddingtonTensor<true>(r, fx_R, fy_R, fz_R, TR);
 	const double FnL = (DIR == 0) ? Fx_L : (DIR == 1) ? Fy_L : Fz_L;
 	const double FnR = (DIR == 0) ? Fx_R : (DIR == 1) ? Fy_R : Fz_R;
 	double FL[NRAD] = {FnL, TL[DIR][0] * erad_L, TL[DIR][1] * erad_L, TL[DIR][2] * erad_L};
@@ -596,6 +605,8 @@ QK_DEV void radSourceCell(RadT const &r, Eos const &eos, double U[10], double sr
 			const double fz = divBy(Frad_t0[2], RcE);
 			const double F_coeff = chat * rho * kappaF * dt * lorentz_factor;
 			double Tedd[3][3];
+			// (KEEP_NAN = false on purpose: a group left without energy by the solve still gets the finite tensor of f = 0 here, as before — the
+			// exchange kernels are pinned by their own tests and not part of the transport fix; qk_rad_mg_device.hpp restores the NaN at its call site)
 			eddingtonTensor(r, fx, fy, fz, Tedd);
 #pragma unroll
 			for (int n = 0; n < 3; ++n) {

@@ -82,14 +82,53 @@ template <class A> QK_DEV void storeRadNT(A const &X, int64_t o, int comp0, cons
 	}
 }
 
-// cons -> prim of one cell (radiation_system.hpp:603-610)
-QK_DEV void radPrim(Rad const &r, const double c[NRAD], double p[NRAD])
+QK_DEV auto notFinite(double x) -> bool { return __builtin_amdgcn_class(x, 0x207); } // NaN, -inf, +inf
+
+// cons -> prim of one cell (radiation_system.hpp:603-610).  Returns whether the cell holds a non-number (NaN or infinity in any primitive): the
+// reconstruction of every stencil with such a cell takes the reference's own comparisons (radPpmEdges / radMC below).
+QK_DEV auto radPrim(Rad const &r, const double c[NRAD], double p[NRAD]) -> bool
 {
 	p[0] = c[0];
-	const Recip RcE = recipOf(r.c * c[0]); // three quotients, one refined reciprocal (qk_device.hpp: same bits as three `/`)
+	const double cE = r.c * c[0];
+	const Recip RcE = recipOf(cE); // three quotients, one refined reciprocal (qk_device.hpp: same bits as three `/`)
 	p[1] = divBy(c[1], RcE);
 	p[2] = divBy(c[2], RcE);
 	p[3] = divBy(c[3], RcE);
+	const bool odd = notFinite((p[0] + p[1]) + (p[2] + p[3])); // (a sum of finite terms that overflows: flagged too, the slower path gives the same values)
+	// c E = +-0 (a repaired cell with Erad_floor = 0) or +-inf: divBy gives NaN for every numerator, the reference's division +-inf, +-0 or NaN, and
+	// the reference branches on them (inf >= 1 takes the fallback; the limiters of the neighbours see an infinity).  The hardware's reciprocal of
+	// such a denominator is exact (+-inf, +-0), so F * rcp(c E) IS the IEEE quotient; any other denominator keeps the refined form.
+	if (odd && __builtin_amdgcn_class(cE, 0x264)) { // -inf, -0, +0, +inf
+		const double r0 = __builtin_amdgcn_rcp(cE);
+#pragma unroll
+		for (int n = 1; n < NRAD; ++n) {
+			p[n] = c[n] * r0;
+		}
+	}
+	return odd;
+}
+
+// The limiters for operands the fast forms of qk_device.hpp do not serve.  smin / smax (v_min_f64 / v_max_f64) drop a NaN, and the reduced flux of a
+// cell with E = 0 — what the state repair leaves of a negative energy when Erad_floor = 0 — is NaN (or +-inf): the reference's std::min, std::max,
+// std::minmax and clamp hand such a value on, so that the face states of the NEIGHBOURS of such a cell are NaN as well, and a finite state in their
+// place would hide a run the reference counts as failed (its AMREX_ASSERT(!isnan(F))).  A stencil that holds a non-number takes the reference's own
+// comparisons, one by one (the REF forms of MC and ppmEdges, qk_device.hpp); every other stencil keeps
+// the one-instruction forms — same value for ordered operands.  `odd`: a cell of the stencil is flagged by radPrim (three additions and a class test
+// per cell, the flags of a stencil combined in scalar registers).
+QK_DEV auto radMC(bool odd, double a, double b) -> double
+{
+	if (odd) {
+		return MC<true>(a, b);
+	}
+	return MC(a, b);
+}
+QK_DEV void radPpmEdges(bool odd, double qm2, double qm1, double q0, double qp1, double qp2, double &am, double &ap)
+{
+	if (odd) {
+		ppmEdges<true>(qm2, qm1, q0, qp1, qp2, am, ap);
+	} else {
+		ppmEdges(qm2, qm1, q0, qp1, qp2, am, ap);
+	}
 }
 
 // Face states by reconstruction ORDER: 3 PPM (ppmEdges), 2 PLM (hyperbolic_system.hpp:243-246 with the MC limiter, QuokkaSimulation.hpp:1948),
@@ -98,29 +137,29 @@ template <int ORDER> constexpr int RAD_M0 = (ORDER == 3) ? 0 : (ORDER == 2) ? 1 
 template <int ORDER> constexpr int RAD_M1 = (ORDER == 3) ? 5 : (ORDER == 2) ? 4 : 3;
 
 // component n of what cell face-1 gives to the face — PPM: its right edge; PLM: its limited slope
-template <int ORDER> QK_DEV auto radSeedCarry(const double p[6][NRAD], int n) -> double
+template <int ORDER> QK_DEV auto radSeedCarry(const double p[6][NRAD], const bool nf[6], int n) -> double
 {
 	if constexpr (ORDER == 3) {
 		double am, ap;
-		ppmEdges(p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap);
+		radPpmEdges(nf[0] || nf[1] || nf[2] || nf[3] || nf[4], p[0][n], p[1][n], p[2][n], p[3][n], p[4][n], am, ap);
 		return ap;
 	} else if constexpr (ORDER == 2) {
-		return MC(p[3][n] - p[2][n], p[2][n] - p[1][n]);
+		return radMC(nf[1] || nf[2] || nf[3], p[3][n] - p[2][n], p[2][n] - p[1][n]);
 	} else {
 		return 0.0; // (not read)
 	}
 }
 // component n of both states of the face, from the carry and from cell `face`; what that cell gives to the next face becomes the carry
-template <int ORDER> QK_DEV void radStepFace(const double p[6][NRAD], int n, double &carry, double &pL, double &pR)
+template <int ORDER> QK_DEV void radStepFace(const double p[6][NRAD], const bool nf[6], int n, double &carry, double &pL, double &pR)
 {
 	if constexpr (ORDER == 3) {
 		double am, ap;
-		ppmEdges(p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap);
+		radPpmEdges(nf[1] || nf[2] || nf[3] || nf[4] || nf[5], p[1][n], p[2][n], p[3][n], p[4][n], p[5][n], am, ap);
 		pL = carry;
 		pR = am;
 		carry = ap;
 	} else if constexpr (ORDER == 2) {
-		const double rslope = MC(p[4][n] - p[3][n], p[3][n] - p[2][n]);
+		const double rslope = radMC(nf[2] || nf[3] || nf[4], p[4][n] - p[3][n], p[3][n] - p[2][n]);
 		pL = p[2][n] + 0.25 * carry;
 		pR = p[3][n] - 0.25 * rslope;
 		carry = rslope;
@@ -130,12 +169,12 @@ template <int ORDER> QK_DEV void radStepFace(const double p[6][NRAD], int n, dou
 	}
 }
 // a face on its own: the first step of a march
-template <int ORDER> QK_DEV void radFaceStates(const double p[6][NRAD], double pL[NRAD], double pR[NRAD])
+template <int ORDER> QK_DEV void radFaceStates(const double p[6][NRAD], const bool nf[6], double pL[NRAD], double pR[NRAD])
 {
 #pragma unroll
 	for (int n = 0; n < NRAD; ++n) {
-		double carry = radSeedCarry<ORDER>(p, n);
-		radStepFace<ORDER>(p, n, carry, pL[n], pR[n]);
+		double carry = radSeedCarry<ORDER>(p, nf, n);
+		radStepFace<ORDER>(p, nf, n, carry, pL[n], pR[n]);
 	}
 }
 
@@ -173,13 +212,14 @@ template <int DIR, int ORDER> void launchRadFusedFlux(qk_level *lev, qk_stream s
 		const int dx = unit(DIR, 0), dy = unit(DIR, 1), dz = unit(DIR, 2);
 		const int pg = NRAD * static_cast<int>(blockIdx.z); // component offset of this block's photon group
 		double c[6][NRAD], p[6][NRAD]; // cells i-3 .. i+2 along DIR
+		bool nf[6] = {false, false, false, false, false, false};
 #pragma unroll
 		for (int m = RAD_M0<ORDER>; m <= RAD_M1<ORDER>; ++m) {
 			loadRad(U, U.idx(i + (m - 3) * dx, j + (m - 3) * dy, k + (m - 3) * dz), RAD0 + pg, c[m]);
-			radPrim(rad, c[m], p[m]);
+			nf[m] = radPrim(rad, c[m], p[m]);
 		}
 		double pL[NRAD], pR[NRAD], Fo[NRAD];
-		radFaceStates<ORDER>(p, pL, pR);
+		radFaceStates<ORDER>(p, nf, pL, pR);
 		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(eps_t, b, i, j, k, static_cast<int>(blockIdx.z)));
 		storeRad(F, F.idx(i, j, k), pg, Fo);
 	}, rad.ngroups);
@@ -200,6 +240,7 @@ template <int DIR, int ORDER> struct RadMarch { // the rolling window
 	static constexpr int M0 = RAD_M0<ORDER>, M1 = RAD_M1<ORDER>;
 	static constexpr int AHEAD = M1 - 3; // the cell that enters the window at a face is face + AHEAD
 	double c[6][NRAD], p[6][NRAD]; // cells face-3 .. face+2 along DIR (only M0..M1 are live)
+	bool nf[6] = {false, false, false, false, false, false}; // radPrim's flag of each
 	double carry[NRAD];	       // PPM: right edge of cell face-1; PLM: its limited slope
 
 	// the window of the first face and the carry into it; comp0: the first component of the photon group in U
@@ -208,11 +249,11 @@ template <int DIR, int ORDER> struct RadMarch { // the rolling window
 #pragma unroll
 		for (int m = M0; m <= M1; ++m) {
 			loadRad(U, pen.at(U, face + (m - 3)), comp0, c[m]);
-			radPrim(rad, c[m], p[m]);
+			nf[m] = radPrim(rad, c[m], p[m]);
 		}
 #pragma unroll
 		for (int n = 0; n < NRAD; ++n) {
-			carry[n] = radSeedCarry<ORDER>(p, n);
+			carry[n] = radSeedCarry<ORDER>(p, nf, n);
 		}
 	}
 	// on to the next face: `entering` is the conserved state of the cell AHEAD of it
@@ -225,12 +266,13 @@ template <int DIR, int ORDER> struct RadMarch { // the rolling window
 				c[m][n] = c[m + 1][n];
 				p[m][n] = p[m + 1][n];
 			}
+			nf[m] = nf[m + 1];
 		}
 #pragma unroll
 		for (int n = 0; n < NRAD; ++n) {
 			c[M1][n] = entering[n];
 		}
-		radPrim(rad, c[M1], p[M1]);
+		nf[M1] = radPrim(rad, c[M1], p[M1]);
 	}
 	// the flux of photon group g at `face`, the face the window stands at
 	QK_DEV void flux(Rad const &rad, const qk_array4 *eps_t, int b, RadPencil<DIR> const &pen, int face, int g, double Fo[NRAD])
@@ -238,7 +280,7 @@ template <int DIR, int ORDER> struct RadMarch { // the rolling window
 		double pL[NRAD], pR[NRAD];
 #pragma unroll
 		for (int n = 0; n < NRAD; ++n) {
-			radStepFace<ORDER>(p, n, carry[n], pL[n], pR[n]);
+			radStepFace<ORDER>(p, nf, n, carry[n], pL[n], pR[n]);
 		}
 		radFaceFlux<DIR>(rad, pL, pR, c[2], c[3], Fo, faceEpsilon(eps_t, b, pen.i, pen.j(face), pen.k(face), g));
 	}
@@ -286,18 +328,32 @@ constexpr int RXB = 256, RXOUT = 250;
 constexpr int RXCELLS = RXB - 7; // cells updated per workgroup of the X sweep: threads 3 .. RXB-4 (their right neighbour holds the other face)
 
 // edge pass of lane t: the left edge state of its cell (= the right state of its left face) and, into s_e, what the cell gives to its right face
-template <int ORDER> QK_DEV void radEdgePass(const double (*s_p)[RXB], double (*s_e)[RXB], int t, const double p0[NRAD], double edgeL[NRAD])
+template <int ORDER> QK_DEV void radEdgePass(const double (*s_p)[RXB], bool mine, double (*s_e)[RXB], int t, const double p0[NRAD], double edgeL[NRAD])
 {
 	const int tm2 = max(t - 2, 0), tm1 = max(t - 1, 0), tp1 = min(t + 1, RXB - 1), tp2 = min(t + 2, RXB - 1);
+	// radPrim's flag of the lane's own cell and, for the neighbours of the stencil (PLM: the two inner ones), the same test on the primitives the
+	// edges below read from LDS anyway — one sum over them: a flag array would be the kilobyte of LDS that costs the sweep a workgroup per CU
+	bool odd = mine;
+	if constexpr (ORDER >= 2) {
+		double sum = 0.0;
+#pragma unroll
+		for (int n = 0; n < NRAD; ++n) {
+			sum += s_p[n][tm1] + s_p[n][tp1];
+			if constexpr (ORDER == 3) {
+				sum += s_p[n][tm2] + s_p[n][tp2];
+			}
+		}
+		odd = odd || notFinite(sum);
+	}
 #pragma unroll
 	for (int n = 0; n < NRAD; ++n) {
 		if constexpr (ORDER == 3) {
 			double am, ap;
-			ppmEdges(s_p[n][tm2], s_p[n][tm1], p0[n], s_p[n][tp1], s_p[n][tp2], am, ap);
+			radPpmEdges(odd, s_p[n][tm2], s_p[n][tm1], p0[n], s_p[n][tp1], s_p[n][tp2], am, ap);
 			edgeL[n] = am;
 			s_e[n][t] = ap;
 		} else if constexpr (ORDER == 2) {
-			const double slope = MC(s_p[n][tp1] - p0[n], p0[n] - s_p[n][tm1]);
+			const double slope = radMC(odd, s_p[n][tp1] - p0[n], p0[n] - s_p[n][tm1]);
 			edgeL[n] = p0[n] - 0.25 * slope;
 			s_e[n][t] = slope;
 		} else {
@@ -343,7 +399,7 @@ QK_DEV auto radXSlabFlux(Rad const &rad, qk_box const &bx, int b, int k, const q
 	const int j = bx.lo[1] + jj;
 	double c0[NRAD], p0[NRAD];
 	loadRad(U, U.idx(i, j, k), RAD0 + pg, c0);
-	radPrim(rad, c0, p0);
+	const bool mine = radPrim(rad, c0, p0);
 #pragma unroll
 	for (int n = 0; n < NRAD; ++n) {
 		s_c[n][t] = c0[n];
@@ -351,7 +407,7 @@ QK_DEV auto radXSlabFlux(Rad const &rad, qk_box const &bx, int b, int k, const q
 	}
 	__syncthreads();
 	double edgeL[NRAD];
-	radEdgePass<ORDER>(s_p, s_e, t, p0, edgeL);
+	radEdgePass<ORDER>(s_p, mine, s_e, t, p0, edgeL);
 	__syncthreads();
 	const bool isFace = inside && (i >= bx.lo[0]) && (i <= bx.hi[0] + 1) && (t >= 3) && (t <= RXB - 3);
 	if (!isFace) {
@@ -502,7 +558,9 @@ template <int ORDER, bool STORE> __global__ void __launch_bounds__(RXB) k_rad_sw
 }
 
 // Y and Z sweeps: one thread marches `strip` cells of a pencil along DIR (strip + 1 faces).
-// EPI 0: acc += term (Y); 1: PredictStep update; 2: AddFluxesRK2 update (Z; the strip is the whole pencil then, see RadSweep::U_new).
+// EPI 0: acc += term (Y); 1: PredictStep update; 2: AddFluxesRK2 update (Z; the strip is the whole pencil then, see RadSweep::U_new), each followed by
+// the validity test and repair of the cell — one photon group: the cell's verdict is the group's.  3 / 4: the updates of 1 / 2 stored as they are —
+// several groups: the verdict needs all of them (launchRadRepairGroups, after the last group's sweeps).
 template <int DIR, int ORDER, int EPI, bool STORE>
 __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Rad rad, RadSweep a, int notb, int strip)
 {
@@ -570,7 +628,7 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 			} else {
 #pragma unroll
 				for (int n = 0; n < NRAD; ++n) {
-					if (EPI == 1) {
+					if (EPI == 1 || EPI == 3) {
 						cons[n] = u0v[n] + cons[n]; // radiation_system.hpp:681-690
 					} else {
 						const double U_0 = u0v[n];
@@ -578,8 +636,10 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 						cons[n] = (1.0 - IMEX_a32) * U_0 + IMEX_a32 * U_1 + (0.5 * (cons[n])); // :758-759 with the zero-weight term dropped
 					}
 				}
-				if (!radStateValid(rad, cons)) {
-					amendRadState(rad, cons);
+				if constexpr (EPI <= 2) {
+					if (!radStateValid(rad, cons)) {
+						amendRadState(rad, cons);
+					}
 				}
 				WA4 Un(a.U_new[b]);
 				storeRadNT(Un, pen.at(Un, face - 1), RAD0 + a.pg, cons); // (the new state is not read again by this stage: non-temporal)
@@ -592,8 +652,36 @@ __global__ void __launch_bounds__(256) k_rad_sweep_march(const qk_box *boxes, Ra
 	}
 }
 
-// the three sweeps of one photon group (a.pg)
-template <int ORDER, int STAGE> void launchRadSweeps(qk_level *lev, qk_stream s, Rad rad, RadSweep const &a, int nghost, bool store)
+// isStateValid and amendRadState (radiation_system.hpp:626-665) on a state whose photon groups the fused stage advanced one after the other, each
+// stored unrepaired: the verdict of the whole cell from all its groups, then — in an invalid cell only — the repair of every group, a valid one below
+// its floor included.  Once per cell: amendRadState is not idempotent (a rescaled flux can exceed c E again by a rounding).
+void launchRadRepairGroups(qk_level *lev, qk_stream s, Rad rad, qk_array4 *U_new_t)
+{
+	launchRad(lev, s, 0, -1, "rad_repair_groups", [=] __device__(int b, int i, int j, int k, bool valid) {
+		if (!valid) {
+			return;
+		}
+		WA4 Un(U_new_t[b]);
+		const int64_t o = Un.idx(i, j, k);
+		bool cellValid = true;
+		double cons[NRAD];
+		for (int g = 0; g < rad.ngroups; ++g) {
+			loadRad(Un, o, RAD0 + NRAD * g, cons);
+			cellValid = cellValid && radStateValid(rad, cons);
+		}
+		if (cellValid) {
+			return;
+		}
+		for (int g = 0; g < rad.ngroups; ++g) {
+			loadRad(Un, o, RAD0 + NRAD * g, cons);
+			amendRadState(rad, cons);
+			storeRad(Un, o, RAD0 + NRAD * g, cons);
+		}
+	});
+}
+
+// the three sweeps of one photon group (a.pg); REPAIR: the Z sweep tests and repairs the cell (one group), otherwise it stores the update as it is
+template <int ORDER, int STAGE, bool REPAIR = true> void launchRadSweeps(qk_level *lev, qk_stream s, Rad rad, RadSweep const &a, int nghost, bool store)
 {
 	if (lev->nboxes == 0) {
 		return;
@@ -622,7 +710,7 @@ template <int ORDER, int STAGE> void launchRadSweeps(qk_level *lev, qk_stream s,
 			int notb;
 			const dim3 grid = radMarchGrid(lev, 2, lev->maxlen[2], strip, lev->nboxes, notb);
 			ProfScope ps(lev->ctx, st, "rad_sweep_z");
-			hipLaunchKernelGGL((k_rad_sweep_march<2, ORDER, STAGE, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, strip);
+			hipLaunchKernelGGL((k_rad_sweep_march<2, ORDER, REPAIR ? STAGE : STAGE + 2, STORE>), grid, dim3(64, 4), 0, st, lev->d_boxes, rad, a, notb, strip);
 		}
 	};
 	if (store) {
@@ -860,18 +948,25 @@ int qk_rad_stage_fused(qk_level *lev, qk_stream s, const qk_rad_traits *rt, int 
 		a.dtdx[d] = dt / dx_in[d];
 		a.eps[d] = (wavespeed_eps != nullptr) ? wavespeed_eps[d] : nullptr;
 	}
-	// the photon groups are transported independently (radiation_system.hpp:667-771 loops over them inside one kernel): one set of sweeps per group
+	// The photon groups are transported independently (radiation_system.hpp:667-771 loops over them inside one kernel): one set of sweeps per group.
+	// The state repair is not independent — isStateValid is a property of the whole cell and amendRadState then repairs every group (:626-665) —:
+	// with several groups the sweeps store the updates unrepaired and one pass over the cells gives the verdict afterwards.  A single group keeps
+	// the repair in the Z sweep's epilogue.
+	const bool several = rad.ngroups > 1;
 	dispatchConst1to3(order, [&](auto O) {
 		constexpr int ORDER = decltype(O)::value;
 		for (int g = 0; g < rad.ngroups; ++g) {
 			a.pg = NRAD * g;
 			if (stage == 1) {
-				launchRadSweeps<ORDER, 1>(lev, s, rad, a, 4, store);
+				several ? launchRadSweeps<ORDER, 1, false>(lev, s, rad, a, 4, store) : launchRadSweeps<ORDER, 1>(lev, s, rad, a, 4, store);
 			} else {
-				launchRadSweeps<ORDER, 2>(lev, s, rad, a, 4, store);
+				several ? launchRadSweeps<ORDER, 2, false>(lev, s, rad, a, 4, store) : launchRadSweeps<ORDER, 2>(lev, s, rad, a, 4, store);
 			}
 		}
 	});
+	if (several) {
+		launchRadRepairGroups(lev, s, rad, U_new);
+	}
 	return radStatus(lev, "rad stage_fused");
 }
 

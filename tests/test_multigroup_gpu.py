@@ -185,9 +185,10 @@ def test_marshak_vaytet_runs_to_the_end_on_gpu(ctx):
 
 
 def test_multigroup_transport_in_3d_is_bit_exact(ctx, oracle):
-    """The 3-D flux kernels (LDS slab kernel along x, marching kernels along y / z) and the whole-cell state repair with the group index folded
-    into the grid: RadhydroShockMultigroup on the deck's 64 x 4 x 4 cells in two boxes, a rippled state with structure along y and z, radiation
-    transport only (PredictStep + AddFluxesRK2, no source term: no libm) — bit for bit."""
+    """The 3-D flux kernels (LDS slab kernel along x, marching kernels along y / z) with the group index folded into the grid, through the driver:
+    RadhydroShockMultigroup on the deck's 64 x 4 x 4 cells in two boxes, a rippled state with structure along y and z, radiation transport only
+    (PredictStep + AddFluxesRK2, no source term: no libm) — bit for bit.  This geometry has no seams: the slab of 40 x 4 positions is one X workgroup's,
+    every Y and Z pencil one strip's — the seams of the kernels and the whole-cell state repair are pinned in tests/test_rad_transport_cells_gpu.py."""
     from quokka_amd.radhydro_multigroup import RadShockMGConstants as S, radshock_mg_problem
     n = [64, 4, 4]
     so = oracle.sim(RADSHOCK_MG, 3, n, [0, 0, 0], [S.Lx, 0.001575, 1.0], [0, 1, 1], max_grid_size=[32, 4, 4])
