@@ -675,10 +675,28 @@ int qk_cooling_tabulated(qk_level *lev, qk_stream s, const qk_hydro_traits *t, q
 			 long long *d_counters);
 /* The per-cell functions of src/cooling/TabulatedCooling.hpp a problem evaluates in its own kernels, over n (rho, value) pairs in device memory:
  * ComputeTgasFromEgas (:117-174; value = E_int), ComputeEgasFromTgas (:101-115; value = T), ComputeMMW (:206-220; value = E_int),
- * ComputeCoolingLength (:176-204; value = E_int), cloudy_cooling_function (:82-99; value = T). */
-enum { QK_COOLING_TGAS_FROM_EGAS = 0, QK_COOLING_EGAS_FROM_TGAS = 1, QK_COOLING_MMW = 2, QK_COOLING_LENGTH = 3, QK_COOLING_NET_HEATING = 4 };
+ * ComputeCoolingLength (:176-204; value = E_int), cloudy_cooling_function (:82-99; value = T).
+ * Introspection for tests, the pieces those functions are made of (the tables and gamma are not read): QK_COOLING_LOG10 = log10(value) and
+ * QK_COOLING_INV_SQRT = value^(-1/2) as the selected libm (qk_cooling_set_libm) computes them, QK_COOLING_QUO = cool::quo(rho, value), the
+ * quotient primitive of csrc/qk_cooling_device.hpp (over(n, denOf(d))). */
+enum {
+	QK_COOLING_TGAS_FROM_EGAS = 0,
+	QK_COOLING_EGAS_FROM_TGAS = 1,
+	QK_COOLING_MMW = 2,
+	QK_COOLING_LENGTH = 3,
+	QK_COOLING_NET_HEATING = 4,
+	QK_COOLING_LOG10 = 5,
+	QK_COOLING_INV_SQRT = 6,
+	QK_COOLING_QUO = 7
+};
 int qk_cooling_evaluate(qk_ctx *ctx, qk_stream s, const qk_cloudy_tables *device_tables, double gamma, int what, int64_t n, const double *d_rho, const double *d_value,
 			double *d_out);
+/* Which log10 and x^(-1/2) the cooling kernels of this context call.  QK_COOLING_LIBM_DEVICE (the default): the device libm, as the reference's
+ * std::log10 / std::pow.  QK_COOLING_LIBM_PORTABLE: a second instantiation of the same kernels over a log10 and a 1 / sqrt made of correctly
+ * rounded operations only (csrc/qk_portable_libm.hpp), which a CPU reproduces in every bit — for the tests that hold the kernels to the oracle
+ * cell by cell; slower and 2 ulps from log10, never selected in production.  Takes effect with the next launch. */
+enum { QK_COOLING_LIBM_DEVICE = 0, QK_COOLING_LIBM_PORTABLE = 1 };
+int qk_cooling_set_libm(qk_ctx *ctx, int libm);
 
 /* ------------------------------------------------------------------ arithmetic primitives (introspection for tests)
  * The hand-rolled FP64 division and square root of csrc/qk_device.hpp, which every kernel's "same bits as `/` and sqrt" rests on, over n elements in

@@ -22,9 +22,65 @@
 #include <vector>
 
 #include "eos.hpp"
+#include "portable_libm.hpp"
 
 namespace oracle::cooling
 {
+
+// ---------------------------------------------------------------- the libm hook and the per-cell record (test instrumentation, not the reference's)
+// The per-cell functions make two kinds of libm call: std::log10 (eight places) and std::pow(epsilon, -1 / p) (rk_adaptive_integrate).  glibc's are
+// the default.  LIBM_PORTABLE routes them to portable_libm.hpp, whose results a GPU reproduces in every bit: the kernels' portable instantiation
+// is then held to this file cell by cell.  (prepare_tables keeps its log10: host code on both sides.)
+enum { LIBM_GLIBC = 0, LIBM_PORTABLE = 1 };
+inline auto libm_mode() -> int &
+{
+	static int mode = LIBM_GLIBC;
+	return mode;
+}
+inline auto lm_log10(const double x) -> double { return (libm_mode() == LIBM_PORTABLE) ? portable_libm::log10_portable(x) : std::log10(x); }
+// (the only exponent the integrator passes is -1 / p = -1/2)
+inline auto lm_pow(const double x, const double exponent) -> double
+{
+	return (libm_mode() == LIBM_PORTABLE && exponent == -0.5) ? portable_libm::rsqrt_portable(x) : std::pow(x, exponent);
+}
+
+// which branches the integration of one cell went through, and how often it tried
+enum : unsigned {
+	BR_EMIN = 1U << 0,	      // user_rhs / ComputeTgasFromEgas: E <= E(T_min)
+	BR_EMAX = 1U << 1,	      // E >= E(T_max)
+	BR_NH_LOW = 1U << 2,	      // interpolate2d: log10 n_H below the table (clamped)
+	BR_NH_HIGH = 1U << 3,	      // above
+	BR_YI_QUIRK = 1U << 4,	      // ix == iix and the ordinate yi equals the index iiy (first temperature interval): w11 = 1, no interpolation in T
+	BR_IX_TOP = 1U << 5,	      // ix == iix (last density row)
+	BR_PARABOLA = 1U << 6,	      // cubic_interpolate fell back to quadratic_interpolate
+	BR_SECANT = 1U << 7,	      // quadratic_interpolate fell back to secant_interpolate
+	BR_BISECT = 1U << 8,	      // toms748_solve: the three steps did not halve the bracket, bisection forced
+	BR_EMPTY_BRACKET = 1U << 9,   // ComputeTgasFromEgas: T_lo >= T_hi, NaN
+	BR_SEVEN_REFUSALS = 1U << 10, // rk_adaptive_integrate: no attempt of a step accepted
+	BR_MAX_SUBSTEPS = 1U << 11,   // 2000 steps taken and the end not reached
+	BR_NAN_DT_GUESS = 1U << 12,   // the first step size taken as the whole interval
+	BR_COINCIDE = 1U << 13,	      // toms748_solve: function values closer than 32 DBL_MIN, parabola instead of the cubic
+	BR_ETA_FLOOR = 1U << 14	      // rk_adaptive_integrate: third or later attempt of a step with eta below eta_min_errfail_multiple (raised to 0.1)
+};
+struct cell_record {
+	int attempts = 0;     // rk12_single_step calls
+	int refused = 0;      // of them not accepted
+	int deepest_retry = 0; // the largest k at which an attempt was made
+	int failed_rhs = 0;   // attempts whose right-hand side returned an error
+	int f_evals = 0;      // function evaluations of Algorithm 748
+	unsigned mask = 0;
+};
+inline auto record() -> cell_record *&
+{
+	static thread_local cell_record *r = nullptr;
+	return r;
+}
+inline void mark(unsigned bit)
+{
+	if (record() != nullptr) {
+		record()->mask |= bit;
+	}
+}
 
 // ---------------------------------------------------------------- FastMath.hpp
 inline auto fastlg(const double x) -> double // :33-40
@@ -75,6 +131,11 @@ inline auto interpolate2d(double x, double y, Table1D const &xv, Table1D const &
 	double dx = (xf - xi) / static_cast<double>(xv.end - xv.begin - 1);
 	double dy = (yf - yi) / static_cast<double>(yv.end - yv.begin - 1);
 
+	if (x < xi) {
+		mark(BR_NH_LOW);
+	} else if (xf < x) {
+		mark(BR_NH_HIGH);
+	}
 	x = std::clamp(x, xi, xf);
 	y = std::clamp(y, yi, yf);
 
@@ -93,6 +154,9 @@ inline auto interpolate2d(double x, double y, Table1D const &xv, Table1D const &
 	double w21 = 0;
 	double w22 = 0;
 
+	if (ix == iix) {
+		mark(BR_IX_TOP | ((yi == iiy) ? BR_YI_QUIRK : 0U));
+	}
 	if (ix != iix && iy != iiy) {
 		const double vol = ((x2 - x1) * (y2 - y1));
 		w11 = (x2 - x) * (y2 - y) / vol;
@@ -188,6 +252,7 @@ inline auto quadratic_interpolate(const double &a, const double &b, double const
 	A = safe_div(A - B, d - a, 0.0);
 
 	if (A == 0) {
+		mark(BR_SECANT);
 		return secant_interpolate(a, b, fa, fb);
 	}
 	double c;
@@ -200,6 +265,7 @@ inline auto quadratic_interpolate(const double &a, const double &b, double const
 		c -= safe_div(fa + (B + A * (c - b)) * (c - a), B + A * (2 * c - a - b), 1 + c - a);
 	}
 	if ((c <= a) || (c >= b)) {
+		mark(BR_SECANT);
 		c = secant_interpolate(a, b, fa, fb);
 	}
 	return c;
@@ -220,6 +286,7 @@ inline auto cubic_interpolate(const double &a, const double &b, const double &d,
 	double c = q31 + q32 + q33 + a;
 
 	if ((c <= a) || (c >= b)) {
+		mark(BR_PARABOLA);
 		c = quadratic_interpolate(a, b, d, fa, fb, fd, 3);
 	}
 	return c;
@@ -272,6 +339,7 @@ inline auto toms748_solve(F f, const double &ax, const double &bx, const double 
 		bool prof = (fabs(fa - fb) < min_diff) || (fabs(fa - fd) < min_diff) || (fabs(fa - fe) < min_diff) || (fabs(fb - fd) < min_diff) ||
 			    (fabs(fb - fe) < min_diff) || (fabs(fd - fe) < min_diff);
 		if (prof) {
+			mark(BR_COINCIDE);
 			c = quadratic_interpolate(a, b, d, fa, fb, fd, 2);
 		} else {
 			c = cubic_interpolate(a, b, d, e, fa, fb, fd, fe);
@@ -285,6 +353,7 @@ inline auto toms748_solve(F f, const double &ax, const double &bx, const double 
 		prof = (fabs(fa - fb) < min_diff) || (fabs(fa - fd) < min_diff) || (fabs(fa - fe) < min_diff) || (fabs(fb - fd) < min_diff) ||
 		       (fabs(fb - fe) < min_diff) || (fabs(fd - fe) < min_diff);
 		if (prof) {
+			mark(BR_COINCIDE);
 			c = quadratic_interpolate(a, b, d, fa, fb, fd, 3);
 		} else {
 			c = cubic_interpolate(a, b, d, e, fa, fb, fd, fe);
@@ -315,6 +384,7 @@ inline auto toms748_solve(F f, const double &ax, const double &bx, const double 
 		}
 		e = d;
 		fe = fd;
+		mark(BR_BISECT);
 		bracket(f, a, b, a + (b - a) / 2, fa, fb, d, fd);
 		--count;
 	}
@@ -411,8 +481,8 @@ inline auto cloudy_cooling_function(double const rho, double const T, cloudy_tab
 {
 	const double rhoH = rho * cloudy_H_mass_fraction;
 	const double nH = rhoH / (C::m_p + C::m_e);
-	const double log_nH = std::log10(nH);
-	const double log_T = std::log10(T);
+	const double log_nH = lm_log10(nH);
+	const double log_T = lm_log10(T);
 
 	const double logCool = interpolate2d(log_nH, log_T, tables.log_nH, tables.log_Tgas, tables.cool);
 	const double logHeat = interpolate2d(log_nH, log_T, tables.log_nH, tables.log_Tgas, tables.heat);
@@ -426,7 +496,7 @@ inline auto ComputeEgasFromTgas(double rho, double Tgas, double gamma, cloudy_ta
 {
 	const double rhoH = rho * cloudy_H_mass_fraction;
 	const double nH = rhoH / (C::m_p + C::m_e);
-	const double mu = interpolate2d(std::log10(nH), std::log10(Tgas), tables.log_nH, tables.log_Tgas, tables.meanMolWeight);
+	const double mu = interpolate2d(lm_log10(nH), lm_log10(Tgas), tables.log_nH, tables.log_Tgas, tables.meanMolWeight);
 	const double n = rho / ((C::m_p + C::m_e) * mu);
 	const double Pgas = n * C::k_B * Tgas;
 	const double Egas = Pgas / (gamma - 1.);
@@ -439,15 +509,17 @@ inline auto ComputeTgasFromEgas(double rho, double Egas, double gamma, cloudy_ta
 	const double Eint_max = ComputeEgasFromTgas(rho, tables.T_max, gamma, tables);
 
 	if (Egas <= Eint_min) {
+		mark(BR_EMIN);
 		return tables.T_min;
 	}
 	if (Egas >= Eint_max) {
+		mark(BR_EMAX);
 		return tables.T_max;
 	}
 
 	const double rhoH = rho * cloudy_H_mass_fraction;
 	const double nH = rhoH / (C::m_p + C::m_e);
-	const double log_nH = std::log10(nH);
+	const double log_nH = lm_log10(nH);
 
 	const double C_ = (gamma - 1.) * Egas / (C::k_B * (rho / (C::m_p + C::m_e)));
 
@@ -456,7 +528,7 @@ inline auto ComputeTgasFromEgas(double rho, double Egas, double gamma, cloudy_ta
 	int maxIter = maxIterLimit;
 
 	auto f = [log_nH, C_, &tables](const double &T) noexcept {
-		double const log_T = clamp_mi(std::log10(T), 1., 9.);
+		double const log_T = clamp_mi(lm_log10(T), 1., 9.);
 		double const mu = interpolate2d(log_nH, log_T, tables.log_nH, tables.log_Tgas, tables.meanMolWeight);
 		double const fun = C_ * mu - T;
 		return fun;
@@ -471,10 +543,15 @@ inline auto ComputeTgasFromEgas(double rho, double Egas, double gamma, cloudy_ta
 	if (T_min < T_max) {
 		auto bounds = toms748_solve(f, T_min, T_max, tol, maxIter);
 		T_sol = 0.5 * (bounds.first + bounds.second);
+		if (record() != nullptr) {
+			record()->f_evals += maxIter;
+		}
 
 		if ((maxIter >= maxIterLimit) || std::isnan(T_sol)) {
 			T_sol = NAN;
 		}
+	} else {
+		mark(BR_EMPTY_BRACKET);
 	}
 	return T_sol;
 }
@@ -484,8 +561,8 @@ inline auto ComputeCoolingLength(double rho, double Egas, double gamma, cloudy_t
 	const double Tgas = ComputeTgasFromEgas(rho, Egas, gamma, tables);
 	const double rhoH = rho * cloudy_H_mass_fraction;
 	const double nH = rhoH / (C::m_p + C::m_e);
-	const double log_nH = std::log10(nH);
-	const double log_T = std::log10(Tgas);
+	const double log_nH = lm_log10(nH);
+	const double log_T = lm_log10(Tgas);
 	const double logCool = interpolate2d(log_nH, log_T, tables.log_nH, tables.log_Tgas, tables.cool);
 	const double LambdaCool = fm_pow10(logCool);
 	const double Edot = (rhoH * rhoH) * LambdaCool;
@@ -500,8 +577,8 @@ inline auto ComputeMMW(double rho, double Egas, double gamma, cloudy_tables cons
 	const double Tgas = ComputeTgasFromEgas(rho, Egas, gamma, tables);
 	const double rhoH = rho * cloudy_H_mass_fraction;
 	const double nH = rhoH / (C::m_p + C::m_e);
-	const double log_nH = std::log10(nH);
-	const double log_T = std::log10(Tgas);
+	const double log_nH = lm_log10(nH);
+	const double log_T = lm_log10(Tgas);
 	return interpolate2d(log_nH, log_T, tables.log_nH, tables.log_Tgas, tables.meanMolWeight);
 }
 
@@ -523,8 +600,10 @@ inline auto user_rhs(double /*t*/, std::array<double, 1> &y_data, std::array<dou
 	const double Eint = y_data[0];
 
 	if (Eint <= Eint_min) {
+		mark(BR_EMIN);
 		y_rhs[0] = cloudy_cooling_function(rho, tables.T_min, tables);
 	} else if (Eint >= Eint_max) {
+		mark(BR_EMAX);
 		y_rhs[0] = cloudy_cooling_function(rho, tables.T_max, tables);
 	} else {
 		const double T = ComputeTgasFromEgas(rho, Eint, gamma, tables);
@@ -594,6 +673,10 @@ inline void rk_adaptive_integrate(F &&rhs, double t0, v1 &y0, double t1, void *u
 
 	double time = t0;
 	double dt = std::isnan(dt_guess) ? (t1 - t0) : dt_guess;
+	if (std::isnan(dt_guess)) {
+		mark(BR_NAN_DT_GUESS);
+	}
+	cell_record *const rec = record();
 	v1 &y = y0;
 	v1 yerr{};
 	v1 ynew{};
@@ -607,6 +690,12 @@ inline void rk_adaptive_integrate(F &&rhs, double t0, v1 &y0, double t1, void *u
 		bool step_success = false;
 		for (int k = 0; k < maxRetries; ++k) {
 			int ierr = rk12_single_step(rhs, time, y, dt, ynew, yerr, user_data);
+			if (rec != nullptr) {
+				rec->attempts += 1;
+				rec->refused += 1; // (taken back below when the attempt is accepted)
+				rec->deepest_retry = std::max(rec->deepest_retry, k);
+				rec->failed_rhs += (ierr != 0) ? 1 : 0;
+			}
 
 			double eta = NAN;
 			double epsilon = NAN;
@@ -615,9 +704,12 @@ inline void rk_adaptive_integrate(F &&rhs, double t0, v1 &y0, double t1, void *u
 				eta = eta_retry_failed_rhs;
 			} else {
 				epsilon = error_norm(y, yerr, reltol, abstol);
-				eta = std::pow(epsilon, -1.0 / static_cast<double>(p));
+				eta = lm_pow(epsilon, -1.0 / static_cast<double>(p));
 
 				if (epsilon < 1.0) {
+					if (rec != nullptr) {
+						rec->refused -= 1;
+					}
 					y = ynew;
 					time += dt;
 					if (k == 0) {
@@ -634,14 +726,21 @@ inline void rk_adaptive_integrate(F &&rhs, double t0, v1 &y0, double t1, void *u
 			if (k == 1) {
 				eta = std::min(eta, eta_max_errfail_again);
 			} else if (k > 1) {
+				if (eta < eta_min_errfail_multiple) {
+					mark(BR_ETA_FLOOR);
+				}
 				eta = std::clamp(eta, eta_min_errfail_multiple, eta_max_errfail_again);
 			}
 			dt *= eta;
 		}
 
 		if (!step_success) {
+			mark(BR_SEVEN_REFUSALS);
 			success = false;
 			break;
+		}
+		if (i == maxStepsODEIntegrate - 1 && time < t1) {
+			mark(BR_MAX_SUBSTEPS);
 		}
 
 		if (time >= t1) {

@@ -614,6 +614,39 @@ void orc_cloudy_compute_cooling(void *p, double gamma, double dt, double T_floor
 		U[5 * n + i] = cell[5];
 	}
 }
+// which libm the per-cell functions call from now on: 0 glibc (the default), 1 portable_libm.hpp (cooling.hpp, the hook); not to be changed while
+// another thread evaluates
+void orc_cloudy_set_libm(int mode) { cooling::libm_mode() = mode; }
+// portable_libm.hpp itself: which = 0 log10, 1 x^(-1/2)
+void orc_portable_libm(int which, long n, const double *x, double *out)
+{
+	for (long i = 0; i < n; ++i) {
+		out[i] = (which == 0) ? portable_libm::log10_portable(x[i]) : portable_libm::rsqrt_portable(x[i]);
+	}
+}
+// orc_cloudy_compute_cooling with a record per cell, rec[6][n]: attempts, refused attempts, deepest retry, failed right-hand sides, function
+// evaluations of Algorithm 748, branch mask (cooling.hpp: BR_*)
+void orc_cloudy_cooling_cells(void *p, double gamma, double dt, double T_floor, long n, double *U, int *nsteps, int *rec)
+{
+	auto const &t = *static_cast<cooling::cloudy_tables *>(p);
+	_Pragma("omp parallel for schedule(dynamic, 16)")
+	for (long i = 0; i < n; ++i) {
+		double cell[6];
+		for (int c = 0; c < 6; ++c) {
+			cell[c] = U[c * n + i];
+		}
+		cooling::cell_record r;
+		cooling::record() = &r;
+		nsteps[i] = cooling::computeCoolingCell(cell, dt, t, T_floor, gamma);
+		cooling::record() = nullptr;
+		U[4 * n + i] = cell[4];
+		U[5 * n + i] = cell[5];
+		const int fields[6] = {r.attempts, r.refused, r.deepest_retry, r.failed_rhs, r.f_evals, static_cast<int>(r.mask)};
+		for (int c = 0; c < 6; ++c) {
+			rec[c * n + i] = fields[c];
+		}
+	}
+}
 
 // ------------------------------------------------------------------ the matter-radiation exchange, cell by cell
 // The radiation and EOS traits of one single-group problem as a closed set: the fields of qk_rad_traits / qk_hydro_traits (include/quokka_amd.h)

@@ -607,8 +607,15 @@ class OracleCloudy:
     Heating, MMW as H5Dread delivers them)"""
     TGAS_FROM_EGAS, EGAS_FROM_TGAS, MMW, COOLING_LENGTH, NET_HEATING = range(5)
 
-    def __init__(self, arrays: dict, variant: str = "direct"):
+    # the branch mask of cooling_cells (oracle/cooling.hpp: BR_*)
+    BRANCHES = ("emin", "emax", "nh_low", "nh_high", "yi_quirk", "ix_top", "parabola", "secant", "bisect", "empty_bracket", "seven_refusals",
+                "max_substeps", "nan_dt_guess", "coincide", "eta_floor")
+
+    def __init__(self, arrays: dict, variant: str = "direct", libm: str = "glibc"):
+        """libm: "glibc" — std::log10 / std::pow, as the reference — or "portable": oracle/portable_libm.hpp, the functions a GPU reproduces bit for
+        bit (the kernels' portable instantiation is compared with this one)"""
         self.o = Oracle(variant)
+        self.libm = {"glibc": 0, "portable": 1}[libm]
         L = self.lib = self.o.lib
         L.orc_cloudy_create.restype = C.c_void_p
         DP = C.POINTER(C.c_double)
@@ -618,6 +625,9 @@ class OracleCloudy:
         L.orc_cloudy_get.argtypes = [C.c_void_p, C.c_int, DP]
         L.orc_cloudy_evaluate.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_long, DP, DP, DP]
         L.orc_cloudy_compute_cooling.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_long, DP, C.POINTER(C.c_int)]
+        L.orc_cloudy_cooling_cells.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_long, DP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.orc_cloudy_set_libm.argtypes = [C.c_int]
+        L.orc_portable_libm.argtypes = [C.c_int, C.c_long, DP, DP]
         a = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
         self.n0, self.n1 = a["Cooling"].shape
         self.h = C.c_void_p(L.orc_cloudy_create(self.n0, self.n1, _dp(a["Parameter1"]), _dp(a["Temperature"]), _dp(a["Cooling"]), _dp(a["Heating"]), _dp(a["MMW"])))
@@ -644,6 +654,7 @@ class OracleCloudy:
         rho = np.ascontiguousarray(rho, dtype=np.float64)
         val = np.ascontiguousarray(val, dtype=np.float64)
         out = np.zeros_like(rho)
+        self.lib.orc_cloudy_set_libm(self.libm)
         self.lib.orc_cloudy_evaluate(self.h, gamma, what, rho.size, _dp(rho), _dp(val), _dp(out))
         return out
 
@@ -652,5 +663,28 @@ class OracleCloudy:
         U = np.ascontiguousarray(U, dtype=np.float64).copy()
         n = U.shape[1]
         ns = np.zeros(n, dtype=np.int32)
+        self.lib.orc_cloudy_set_libm(self.libm)
         self.lib.orc_cloudy_compute_cooling(self.h, gamma, dt, T_floor, n, _dp(U), ns.ctypes.data_as(C.POINTER(C.c_int)))
         return U, ns
+
+    def cooling_cells(self, U: np.ndarray, gamma: float, dt: float, T_floor: float):
+        """compute_cooling with a record per cell: returns (U after, substeps, rec) — rec a dict of int arrays: attempts, refused, deepest_retry,
+        failed_rhs, f_evals (Algorithm 748), mask (bit i = BRANCHES[i])"""
+        U = np.ascontiguousarray(U, dtype=np.float64).copy()
+        n = U.shape[1]
+        ns = np.zeros(n, dtype=np.int32)
+        rec = np.zeros((6, n), dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self.lib.orc_cloudy_set_libm(self.libm)
+        self.lib.orc_cloudy_cooling_cells(self.h, gamma, dt, T_floor, n, _dp(U), ip(ns), ip(rec))
+        return U, ns, dict(zip(("attempts", "refused", "deepest_retry", "failed_rhs", "f_evals", "mask"), rec))
+
+    def bit(self, name: str) -> int:
+        return 1 << self.BRANCHES.index(name)
+
+    def portable_libm(self, which: int, x) -> np.ndarray:
+        """oracle/portable_libm.hpp: which = 0 log10, 1 x^(-1/2)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        self.lib.orc_portable_libm(which, x.size, _dp(x), _dp(out))
+        return out

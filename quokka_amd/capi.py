@@ -16,6 +16,7 @@ ERR_UNSUPPORTED = QK_ERR_UNSUPPORTED
 HOOK_COMPILED = 100  # QK_HOOK_COMPILED: a hook that is the problem's own compiled device function (the library entry points refuse to evaluate it)
 DIR_X1, DIR_X2, DIR_X3 = 0, 1, 2
 ARITH_DIVBY_RECIPOF, ARITH_DIVN, ARITH_RECIPEXACT, ARITH_SQRTN = 0, 1, 2, 3  # qk_arith_evaluate
+COOLING_LIBM_DEVICE, COOLING_LIBM_PORTABLE = 0, 1  # qk_cooling_set_libm
 RIEMANN_HLLC, RIEMANN_LLF, RIEMANN_HLLD = 0, 1, 2
 LIMITER_MINMOD, LIMITER_MC = 0, 1
 BC_REFLECT_ODD, BC_INT_DIR, BC_REFLECT_EVEN, BC_FOEXTRAP, BC_EXT_DIR = -1, 0, 1, 2, 3
@@ -147,6 +148,7 @@ def lib() -> C.CDLL:
     L.qk_cloudy_tables_free.argtypes = [P(CloudyTables)]
     L.qk_cooling_tabulated.argtypes = [vp, vp, P(HydroTraits), vp, P(CloudyTables), cd, cd, vp]
     L.qk_cooling_evaluate.argtypes = [vp, vp, P(CloudyTables), cd, ci, C.c_int64, vp, vp, vp]
+    L.qk_cooling_set_libm.argtypes = [vp, ci]
     L.qk_arith_evaluate.argtypes = [vp, vp, ci, C.c_int64, vp, vp, vp]
     L.qk_profile_num_kernels.argtypes = [vp]
     L.qk_profile_get.argtypes = [vp, ci, P(C.c_char_p), P(C.c_long), P(cd)]
@@ -278,7 +280,7 @@ DECLARED_SYMBOLS = [
     "qk_interp_plan_create", "qk_interp_plan_destroy", "qk_interp_plan_num_items", "qk_interp_plan_item", "qk_InterpFromCoarse",
     "qk_fluxreg_create", "qk_fluxreg_destroy", "qk_fluxreg_num_items", "qk_fluxreg_item", "qk_fluxreg_reset", "qk_fluxreg_save", "qk_fluxreg_restore", "qk_fluxreg_CrseAdd", "qk_fluxreg_FineAdd",
     "qk_fluxreg_Reflux", "qk_fluxreg_set_state_component", "qk_amr_tile_flags", "qk_amr_tile_flags_periodic", "qk_amr_cluster_tiles", "qk_amr_cluster_berger_rigoutsos", "qk_copy_box",
-    "qk_cloudy_tables_read", "qk_cloudy_tables_free", "qk_cooling_tabulated", "qk_cooling_evaluate", "qk_arith_evaluate",
+    "qk_cloudy_tables_read", "qk_cloudy_tables_free", "qk_cooling_tabulated", "qk_cooling_evaluate", "qk_cooling_set_libm", "qk_arith_evaluate",
     "qk_fluxreg_create_crse_part", "qk_pcopy_plan_create", "qk_pcopy_plan_destroy", "qk_pcopy_plan_num_peers", "qk_pcopy_plan_peer", "qk_pcopy_plan_num_items",
     "qk_pcopy_plan_item", "qk_ParallelCopy_local", "qk_ParallelCopy_pack", "qk_ParallelCopy_unpack",
     "qk_tracer_plan_create", "qk_tracer_plan_destroy", "qk_tracer_plan_lattice", "qk_tracer_InitOnePerCell", "qk_tracer_AdvectWithUmac", "qk_tracer_Redistribute",

@@ -13,6 +13,7 @@ import torch.distributed as dist
 from . import capi, comm
 
 TGAS_FROM_EGAS, EGAS_FROM_TGAS, MMW, COOLING_LENGTH, NET_HEATING = range(5)
+LOG10, INV_SQRT, QUO = 5, 6, 7  # qk_cooling_evaluate, introspection for tests: the libm calls and the quotient primitive the kernels are made of
 MAX_SUBSTEPS = 2000  # maxStepsODEIntegrate (src/math/ODEIntegrate.hpp:120)
 
 
@@ -62,6 +63,12 @@ class TabulatedCooling:
         nmax, nsum = int(t[0].item()), int(t[1].item())
         self.last = (nsum / max(s.CountCells(), 1), nmax)
         return nmax < MAX_SUBSTEPS
+
+    def set_libm(self, portable: bool) -> None:
+        """qk_cooling_set_libm: False — the default — the device libm; True the portable instantiation of the kernels, whose log10 and x^(-1/2) a
+        CPU reproduces in every bit (tests only).  A setting of the CONTEXT: it holds for every cooling call on it until set back."""
+        c = self.sim.ctx
+        c.check(c.L.qk_cooling_set_libm(c.h, capi.COOLING_LIBM_PORTABLE if portable else capi.COOLING_LIBM_DEVICE), "qk_cooling_set_libm")
 
     def evaluate(self, what: int, rho: torch.Tensor, value: torch.Tensor) -> torch.Tensor:
         """the per-cell functions of TabulatedCooling.hpp:82-220 over arrays (see qk_cooling_evaluate)"""

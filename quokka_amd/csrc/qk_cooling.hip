@@ -43,7 +43,9 @@ auto tablesOf(const qk_cloudy_tables *t) -> cool::Tables
 // front): with one cell per thread a wave runs as long as its slowest lane while the others idle (6x on a log-uniform multiphase medium).  Here a
 // lane that finishes its cell stores it and takes the next cell index from a global counter; every trip of the loop is one attempt of a substep
 // (cool::heunAttempt) of whatever cell the lane holds, so the lanes of a wave stay busy until the queue is empty.  Cells are numbered box by box
-// with the largest box's extents (indices outside a smaller box are skipped).
+// with the largest box's extents (indices outside a smaller box are skipped).  M: the libm policy (cool::LibmNative in production; cool::LibmPortable is
+// the instantiation the tests hold to the oracle in every bit, qk_cooling_set_libm).
+template <class M>
 __global__ void __launch_bounds__(256) k_cooling_tabulated(const qk_box *boxes, int nboxes, int max0, int max1, int max2, qk_array4 *state_t, cool::Tables tab, double gamma,
 							   double dt, double T_floor, long long *counters, unsigned long long *queue)
 {
@@ -88,9 +90,9 @@ __global__ void __launch_bounds__(256) k_cooling_tabulated(const qk_box *boxes, 
 				// RadSystem::ComputeEintFromEgas (radiation_system.hpp:1288-1297)
 				const double Ekin = (px * px + py * py + pz * pz) / (2.0 * rho);
 				Eint0 = *pE - Ekin;
-				cc = cool::cellCool(tab, rho, gamma);
-				abstol = reltol_floor * cool::egasFromTgasAt(tab, rho, cc.X, T_floor, gamma);
-				cool::heunBegin(tab, cc, Eint0, dt, s);
+				cc = cool::cellCool<M>(tab, rho, gamma);
+				abstol = reltol_floor * cool::egasFromTgasAt<M>(tab, rho, cc.X, T_floor, gamma);
+				cool::heunBegin<M>(tab, cc, Eint0, dt, s);
 				have = true;
 				break;
 			}
@@ -99,7 +101,7 @@ __global__ void __launch_bounds__(256) k_cooling_tabulated(const qk_box *boxes, 
 			break; // the queue is empty and every lane of the wave has stored its last cell
 		}
 		if (have) {
-			cool::heunAttempt(tab, cc, dt, rtol, abstol, s);
+			cool::heunAttempt<M>(tab, cc, dt, rtol, abstol, s);
 			if (s.nsteps >= 0) {
 				const double dEint = s.E - Eint0;
 				*pE += dEint;
@@ -121,6 +123,7 @@ __global__ void __launch_bounds__(256) k_cooling_tabulated(const qk_box *boxes, 
 	}
 }
 
+template <class M>
 __global__ void __launch_bounds__(256) k_cooling_evaluate(cool::Tables tab, double gamma, int what, int64_t n, const double *rho, const double *val, double *out)
 {
 	const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -130,19 +133,39 @@ __global__ void __launch_bounds__(256) k_cooling_evaluate(cool::Tables tab, doub
 	cool::prepare(tab);
 	switch (what) {
 	case QK_COOLING_TGAS_FROM_EGAS:
-		out[t] = cool::tgasFromEgas(tab, rho[t], val[t], gamma);
+		out[t] = cool::tgasFromEgas<M>(tab, rho[t], val[t], gamma);
 		break;
 	case QK_COOLING_EGAS_FROM_TGAS:
-		out[t] = cool::egasFromTgas(tab, rho[t], val[t], gamma);
+		out[t] = cool::egasFromTgas<M>(tab, rho[t], val[t], gamma);
 		break;
 	case QK_COOLING_MMW:
-		out[t] = cool::meanMolecularWeight(tab, rho[t], val[t], gamma);
+		out[t] = cool::meanMolecularWeight<M>(tab, rho[t], val[t], gamma);
 		break;
 	case QK_COOLING_LENGTH:
-		out[t] = cool::coolingLength(tab, rho[t], val[t], gamma);
+		out[t] = cool::coolingLength<M>(tab, rho[t], val[t], gamma);
 		break;
 	default:
-		out[t] = cool::netHeating(tab, rho[t], val[t]);
+		out[t] = cool::netHeating<M>(tab, rho[t], val[t]);
+		break;
+	}
+}
+
+// the pieces the kernels above are made of, element by element (QK_COOLING_LOG10 ...): the policy's two libm calls and the quotient primitive
+template <class M> __global__ void __launch_bounds__(256) k_cooling_primitives(int what, int64_t n, const double *rho, const double *val, double *out)
+{
+	const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+	if (t >= n) {
+		return;
+	}
+	switch (what) {
+	case QK_COOLING_LOG10:
+		out[t] = M::log10of(val[t]);
+		break;
+	case QK_COOLING_INV_SQRT:
+		out[t] = M::invSqrt(val[t]);
+		break;
+	default:
+		out[t] = cool::quo(rho[t], val[t]);
 		break;
 	}
 }
@@ -279,8 +302,9 @@ int qk_cooling_tabulated(qk_level *lev, qk_stream s, const qk_hydro_traits *t, q
 	const long long cells = static_cast<long long>(lev->maxlen[0]) * lev->maxlen[1] * lev->maxlen[2] * lev->nboxes;
 	const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(256LL * 8, (cells + 255) / 256)));
 	ProfScope ps(lev->ctx, static_cast<hipStream_t>(s), "cooling_tabulated");
-	hipLaunchKernelGGL(k_cooling_tabulated, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(s), lev->d_boxes, lev->nboxes, lev->maxlen[0], lev->maxlen[1],
-			   lev->maxlen[2], state_t, tablesOf(device_tables), t->gamma, dt, T_floor, d_counters, queue);
+	auto *kernel = (lev->ctx->cooling_libm == QK_COOLING_LIBM_PORTABLE) ? k_cooling_tabulated<cool::LibmPortable> : k_cooling_tabulated<cool::LibmNative>;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(s), lev->d_boxes, lev->nboxes, lev->maxlen[0], lev->maxlen[1], lev->maxlen[2],
+			   state_t, tablesOf(device_tables), t->gamma, dt, T_floor, d_counters, queue);
 	const hipError_t e = hipGetLastError();
 	return (e == hipSuccess) ? QK_OK : setError(lev->ctx, QK_ERR_HIP, "cooling_tabulated", hipGetErrorString(e));
 }
@@ -289,12 +313,29 @@ int qk_cooling_evaluate(qk_ctx *ctx, qk_stream s, const qk_cloudy_tables *device
 			double *d_out)
 {
 	QK_REQUIRE(ctx, device_tables != nullptr && d_rho != nullptr && d_val != nullptr && d_out != nullptr, "cooling_evaluate: NULL argument");
-	QK_REQUIRE(ctx, what >= QK_COOLING_TGAS_FROM_EGAS && what <= QK_COOLING_NET_HEATING, "cooling_evaluate: unknown quantity");
+	QK_REQUIRE(ctx, what >= QK_COOLING_TGAS_FROM_EGAS && what <= QK_COOLING_QUO, "cooling_evaluate: unknown quantity");
 	if (n <= 0) {
 		return QK_OK;
 	}
-	hipLaunchKernelGGL(k_cooling_evaluate, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(s), tablesOf(device_tables), gamma, what,
-			   n, d_rho, d_val, d_out);
+	const bool portable = (ctx->cooling_libm == QK_COOLING_LIBM_PORTABLE);
+	const dim3 grid(static_cast<unsigned>((n + 255) / 256));
+	if (what > QK_COOLING_NET_HEATING) {
+		auto *kernel = portable ? k_cooling_primitives<cool::LibmPortable> : k_cooling_primitives<cool::LibmNative>;
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, static_cast<hipStream_t>(s), what, n, d_rho, d_val, d_out);
+	} else {
+		auto *kernel = portable ? k_cooling_evaluate<cool::LibmPortable> : k_cooling_evaluate<cool::LibmNative>;
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, static_cast<hipStream_t>(s), tablesOf(device_tables), gamma, what, n, d_rho, d_val, d_out);
+	}
 	const hipError_t e = hipGetLastError();
 	return (e == hipSuccess) ? QK_OK : setError(ctx, QK_ERR_HIP, "cooling_evaluate", hipGetErrorString(e));
+}
+
+int qk_cooling_set_libm(qk_ctx *ctx, int libm)
+{
+	if (ctx == nullptr) {
+		return QK_ERR_INVALID;
+	}
+	QK_REQUIRE(ctx, libm == QK_COOLING_LIBM_DEVICE || libm == QK_COOLING_LIBM_PORTABLE, "cooling_set_libm: unknown libm");
+	ctx->cooling_libm = libm;
+	return QK_OK;
 }

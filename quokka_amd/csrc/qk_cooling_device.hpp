@@ -13,6 +13,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "qk_portable_libm.hpp"
+
 #ifndef QK_HD
 #if defined(__HIPCC__)
 #define QK_HD __host__ __device__ inline
@@ -53,6 +55,19 @@ QK_HD auto clampi(int v, int lo, int hi) -> int { return (v < lo) ? lo : (hi < v
 QK_HD auto signOf(double v) -> int { return (0.0 < v) - (v < 0.0); }
 QK_HD auto isNan(double v) -> bool { return v != v; }
 
+// The two libm calls of the algorithm, log10 and x^(-1/2) (std::pow(epsilon, -1.0 / p), ODEIntegrate.hpp:176), as a policy of the functions that
+// make them.  LibmNative — the default, what every caller outside the tests gets — is the platform's libm: glibc on the host, the device library
+// in a kernel; the two differ in the last bit of some results.  LibmPortable (qk_portable_libm.hpp) gives the same bits on both: the instantiation
+// the tests compare with the oracle cell by cell (qk_cooling_set_libm).
+struct LibmNative {
+	QK_HD static auto log10of(double x) -> double { return log10(x); }
+	QK_HD static auto invSqrt(double x) -> double { return pow(x, -1.0 / 2.0); }
+};
+struct LibmPortable {
+	QK_HD static auto log10of(double x) -> double { return portable::log10(x); }
+	QK_HD static auto invSqrt(double x) -> double { return portable::rsqrt(x); }
+};
+
 // FastMath::pow10 (src/math/FastMath.hpp:42-49,68-72): 2^x with the fractional part of x taken linearly
 QK_HD auto fastPow10(double x) -> double
 {
@@ -74,8 +89,14 @@ QK_HD auto fastLog10(double x) -> double
 
 // Quotients.  The reference divides; a correctly rounded quotient does not depend on how it is formed.  On the device a divisor shared by several
 // quotients (the cell volume of the four interpolation weights, the axis spacing) is inverted once — v_rcp_f64 refined by two Newton steps — and
-// each quotient is the product with that reciprocal corrected by its fma residual: the IEEE quotient for operands in the normal range (all of them
-// here are differences of table ordinates, O(0.01 ... 10)), 3 instructions instead of the ~35 of a division.  The host divides.
+// each quotient is the product with that reciprocal corrected by its fma residual, 3 instructions instead of the ~35 of a division.  The host
+// divides.  The recipe of recipOf / divBy (qk_device.hpp), with their range: the bits of IEEE for 2^-996 <= |d|, |n|, |n / d| <= 2^1004
+// (tests/test_cooling_cells_gpu.py: random operands, the neighbours of rounding midpoints, the exponent ladder).  The operands here: differences of
+// table ordinates, O(0.01 ... 10), in the weights; in Algorithm 748 temperatures and function values up to 1e9 K over their differences, down to
+// 1e-5 of them — and DBL_MAX, the sentinel of guardedQuotient, as a numerator.  The guard of guardedQuotient lets DBL_MAX through to quo only over
+// |d| >= 1, where the quotient is finite and equals IEEE's (tested over 1 <= |d| < 2^900).  Outside the range, as observed: a zero, infinite or NaN
+// denominator gives NaN (IEEE: +-inf, 0, NaN), an infinite numerator or a quotient that overflows gives NaN (IEEE: +-inf), a zero numerator a zero
+// of either sign.  No cell of the test sets reaches any of these (every cell equals the oracle, which divides, in every bit).
 struct Den {
 	double d, r;
 };
@@ -210,48 +231,48 @@ struct CellCool {
 
 // cloudy_cooling_function (TabulatedCooling.hpp:82-99): net heating rate per volume, (rho X)^2 (10^heat - 10^cool); one set of weights serves both
 // tables (t prepared)
-QK_HD auto netHeatingAt(Tables const &t, double rhoH, AxisPos const &X, double T) -> double
+template <class M = LibmNative> QK_HD auto netHeatingAt(Tables const &t, double rhoH, AxisPos const &X, double T) -> double
 {
-	const Weights W = weightsOf(t, X, temperatureAxis(t, log10(T)));
+	const Weights W = weightsOf(t, X, temperatureAxis(t, M::log10of(T)));
 	const double logCool = weighted(t, t.cool, W);
 	const double logHeat = weighted(t, t.heat, W);
 	const double netLambda = fastPow10(logHeat) - fastPow10(logCool);
 	return (rhoH * rhoH) * netLambda;
 }
-QK_HD auto netHeating(Tables const &t0, double rho, double T) -> double
+template <class M = LibmNative> QK_HD auto netHeating(Tables const &t0, double rho, double T) -> double
 {
 	const Tables t = preparedCopy(t0);
 	const double rhoH = rho * H_mass_fraction;
 	const double nH = rhoH / t.m_H;
-	return netHeatingAt(t, rhoH, densityAxis(t, log10(nH)), T);
+	return netHeatingAt<M>(t, rhoH, densityAxis(t, M::log10of(nH)), T);
 }
 
 // ComputeEgasFromTgas (TabulatedCooling.hpp:101-115) (t prepared)
-QK_HD auto egasFromTgasAt(Tables const &t, double rho, AxisPos const &X, double Tgas, double gamma) -> double
+template <class M = LibmNative> QK_HD auto egasFromTgasAt(Tables const &t, double rho, AxisPos const &X, double Tgas, double gamma) -> double
 {
-	const double mu = lookup(t, t.mmw, X, log10(Tgas));
+	const double mu = lookup(t, t.mmw, X, M::log10of(Tgas));
 	const double n = rho / (t.m_H * mu);
 	const double Pgas = n * t.k_B * Tgas;
 	return Pgas / (gamma - 1.);
 }
-QK_HD auto egasFromTgas(Tables const &t0, double rho, double Tgas, double gamma) -> double
+template <class M = LibmNative> QK_HD auto egasFromTgas(Tables const &t0, double rho, double Tgas, double gamma) -> double
 {
 	const Tables t = preparedCopy(t0);
 	const double rhoH = rho * H_mass_fraction;
 	const double nH = rhoH / t.m_H;
-	return egasFromTgasAt(t, rho, densityAxis(t, log10(nH)), Tgas, gamma);
+	return egasFromTgasAt<M>(t, rho, densityAxis(t, M::log10of(nH)), Tgas, gamma);
 }
 // (t prepared)
-QK_HD auto cellCool(Tables const &t, double rho, double gamma) -> CellCool
+template <class M = LibmNative> QK_HD auto cellCool(Tables const &t, double rho, double gamma) -> CellCool
 {
 	CellCool c;
 	c.rho = rho;
 	c.gamma = gamma;
 	c.rhoH = rho * H_mass_fraction;
-	c.log_nH = log10(c.rhoH / t.m_H);
+	c.log_nH = M::log10of(c.rhoH / t.m_H);
 	c.X = densityAxis(t, c.log_nH);
-	c.Emin = egasFromTgasAt(t, rho, c.X, t.T_min, gamma);
-	c.Emax = egasFromTgasAt(t, rho, c.X, t.T_max, gamma);
+	c.Emin = egasFromTgasAt<M>(t, rho, c.X, t.T_min, gamma);
+	c.Emax = egasFromTgasAt<M>(t, rho, c.X, t.T_max, gamma);
 	c.kBn = t.k_B * (rho / t.m_H);
 	return c;
 }
@@ -448,13 +469,13 @@ template <class F> QK_HD void solve748(F const &f, double ax, double bx, double 
 
 // ComputeTgasFromEgas (TabulatedCooling.hpp:117-174): T with mu(n_H, T) C = T, C = (gamma - 1) E / (k_B rho / m_H); NaN when the bracket is empty or
 // the iteration limit is reached
-QK_HD auto tgasInTable(Tables const &t, CellCool const &c, double Egas) -> double // (Emin < Egas < Emax)
+template <class M = LibmNative> QK_HD auto tgasInTable(Tables const &t, CellCool const &c, double Egas) -> double // (Emin < Egas < Emax)
 {
 	const double C = (c.gamma - 1.) * Egas / c.kBn;
 	const double reltol = 1.0e-5;
 	const int maxIterLimit = 100;
 	auto f = [&](double T) {
-		const double log_T = clampd(log10(T), 1., 9.);
+		const double log_T = clampd(M::log10of(T), 1., 9.);
 		const double mu = lookup(t, t.mmw, c.X, log_T);
 		return C * mu - T;
 	};
@@ -472,37 +493,37 @@ QK_HD auto tgasInTable(Tables const &t, CellCool const &c, double Egas) -> doubl
 	}
 	return T_sol;
 }
-QK_HD auto tgasFromEgas(Tables const &t0, double rho, double Egas, double gamma) -> double
+template <class M = LibmNative> QK_HD auto tgasFromEgas(Tables const &t0, double rho, double Egas, double gamma) -> double
 {
 	const Tables t = preparedCopy(t0);
-	const CellCool c = cellCool(t, rho, gamma);
+	const CellCool c = cellCool<M>(t, rho, gamma);
 	if (Egas <= c.Emin) {
 		return t.T_min;
 	}
 	if (Egas >= c.Emax) {
 		return t.T_max;
 	}
-	return tgasInTable(t, c, Egas);
+	return tgasInTable<M>(t, c, Egas);
 }
 
 // ComputeMMW (TabulatedCooling.hpp:206-220)
-QK_HD auto meanMolecularWeight(Tables const &t0, double rho, double Egas, double gamma) -> double
+template <class M = LibmNative> QK_HD auto meanMolecularWeight(Tables const &t0, double rho, double Egas, double gamma) -> double
 {
 	const Tables t = preparedCopy(t0);
-	const double Tgas = tgasFromEgas(t, rho, Egas, gamma);
+	const double Tgas = tgasFromEgas<M>(t, rho, Egas, gamma);
 	const double rhoH = rho * H_mass_fraction;
 	const double nH = rhoH / t.m_H;
-	return lookup(t, t.mmw, densityAxis(t, log10(nH)), log10(Tgas));
+	return lookup(t, t.mmw, densityAxis(t, M::log10of(nH)), M::log10of(Tgas));
 }
 
 // ComputeCoolingLength (TabulatedCooling.hpp:176-204): c_s t_cool with the cooling part of the table only
-QK_HD auto coolingLength(Tables const &t0, double rho, double Egas, double gamma) -> double
+template <class M = LibmNative> QK_HD auto coolingLength(Tables const &t0, double rho, double Egas, double gamma) -> double
 {
 	const Tables t = preparedCopy(t0);
-	const double Tgas = tgasFromEgas(t, rho, Egas, gamma);
+	const double Tgas = tgasFromEgas<M>(t, rho, Egas, gamma);
 	const double rhoH = rho * H_mass_fraction;
 	const double nH = rhoH / t.m_H;
-	const Weights W = weightsOf(t, densityAxis(t, log10(nH)), temperatureAxis(t, log10(Tgas)));
+	const Weights W = weightsOf(t, densityAxis(t, M::log10of(nH)), temperatureAxis(t, M::log10of(Tgas)));
 	const double logCool = weighted(t, t.cool, W);
 	const double LambdaCool = fastPow10(logCool);
 	const double Edot = (rhoH * rhoH) * LambdaCool;
@@ -513,19 +534,19 @@ QK_HD auto coolingLength(Tables const &t0, double rho, double Egas, double gamma
 }
 
 // user_rhs (TabulatedCooling.hpp:222-256): dE_int/dt; false when the temperature iteration failed
-QK_HD auto heatingRate(Tables const &t, CellCool const &c, double Eint, double &rate) -> bool
+template <class M = LibmNative> QK_HD auto heatingRate(Tables const &t, CellCool const &c, double Eint, double &rate) -> bool
 {
 	if (Eint <= c.Emin) {
-		rate = netHeatingAt(t, c.rhoH, c.X, t.T_min);
+		rate = netHeatingAt<M>(t, c.rhoH, c.X, t.T_min);
 	} else if (Eint >= c.Emax) {
-		rate = netHeatingAt(t, c.rhoH, c.X, t.T_max);
+		rate = netHeatingAt<M>(t, c.rhoH, c.X, t.T_max);
 	} else {
-		const double T = tgasInTable(t, c, Eint);
+		const double T = tgasInTable<M>(t, c, Eint);
 		if (isNan(T)) {
 			rate = NAN;
 			return false;
 		}
-		rate = netHeatingAt(t, c.rhoH, c.X, T);
+		rate = netHeatingAt<M>(t, c.rhoH, c.X, T);
 	}
 	return true;
 }
@@ -542,10 +563,10 @@ struct HeunState {
 	int step, retry;
 	int nsteps; // >= 0: finished (the number of steps; maxSubsteps = failure)
 };
-QK_HD void heunBegin(Tables const &t, CellCool const &c, double E0, double dt_total, HeunState &s)
+template <class M = LibmNative> QK_HD void heunBegin(Tables const &t, CellCool const &c, double E0, double dt_total, HeunState &s)
 {
 	double rate0 = NAN;
-	heatingRate(t, c, E0, rate0);
+	heatingRate<M>(t, c, E0, rate0);
 	const double dt_guess = 0.1 * fabs(E0 / rate0);
 	s.E = E0;
 	s.time = 0;
@@ -554,7 +575,7 @@ QK_HD void heunBegin(Tables const &t, CellCool const &c, double E0, double dt_to
 	s.retry = 0;
 	s.nsteps = -1;
 }
-QK_HD void heunAttempt(Tables const &t, CellCool const &c, double dt_total, double reltol, double abstol, HeunState &s)
+template <class M = LibmNative> QK_HD void heunAttempt(Tables const &t, CellCool const &c, double dt_total, double reltol, double abstol, HeunState &s)
 {
 	if (s.retry == 0 && (s.time + s.dt) > dt_total) { // (the head of the step loop)
 		s.dt = dt_total - s.time;
@@ -562,10 +583,10 @@ QK_HD void heunAttempt(Tables const &t, CellCool const &c, double dt_total, doub
 	const int k = s.retry;
 	double eta = NAN;
 	double k1 = NAN, k2 = NAN;
-	bool ok = heatingRate(t, c, s.E, k1);
+	bool ok = heatingRate<M>(t, c, s.E, k1);
 	if (ok) {
 		k1 *= s.dt;
-		ok = heatingRate(t, c, s.E + k1, k2);
+		ok = heatingRate<M>(t, c, s.E + k1, k2);
 	}
 	if (!ok) {
 		eta = 0.5;
@@ -575,7 +596,7 @@ QK_HD void heunAttempt(Tables const &t, CellCool const &c, double dt_total, doub
 		const double Eerr = -0.5 * k1 + 0.5 * k2;
 		const double w = 1. / (reltol * s.E + abstol);
 		const double epsilon = sqrt(((Eerr * Eerr) * (w * w)) / 1);
-		eta = pow(epsilon, -1.0 / 2.0);
+		eta = M::invSqrt(epsilon);
 		if (epsilon < 1.0) { // accepted
 			s.E = Enew;
 			s.time += s.dt;
@@ -602,14 +623,14 @@ QK_HD void heunAttempt(Tables const &t, CellCool const &c, double dt_total, doub
 		s.nsteps = maxSubsteps; // no attempt of this step was accepted
 	}
 }
-QK_HD auto integrateCooling(Tables const &t0, double rho, double gamma, double &E, double dt_total, double reltol, double abstol) -> int
+template <class M = LibmNative> QK_HD auto integrateCooling(Tables const &t0, double rho, double gamma, double &E, double dt_total, double reltol, double abstol) -> int
 {
 	const Tables t = preparedCopy(t0);
-	const CellCool c = cellCool(t, rho, gamma);
+	const CellCool c = cellCool<M>(t, rho, gamma);
 	HeunState s;
-	heunBegin(t, c, E, dt_total, s);
+	heunBegin<M>(t, c, E, dt_total, s);
 	while (s.nsteps < 0) {
-		heunAttempt(t, c, dt_total, reltol, abstol, s);
+		heunAttempt<M>(t, c, dt_total, reltol, abstol, s);
 	}
 	E = s.E;
 	return s.nsteps;

@@ -33,6 +33,7 @@ struct qk_ctx {
 	std::vector<qk_prof_pending> prof_pending;
 	std::vector<hipEvent_t> prof_free_events;
 	int *counter_slots = nullptr; // qk_rad_ops.hip: spread iteration / failure counters (owned)
+	int cooling_libm = 0; // qk_cooling_set_libm: which instantiation of the cooling kernels is launched (0: the device libm)
 };
 
 struct qk_level {
