@@ -705,7 +705,7 @@ int qk_cooling_set_libm(qk_ctx *ctx, int libm);
 enum { QK_ARITH_DIVBY_RECIPOF = 0, QK_ARITH_DIVN = 1, QK_ARITH_RECIPEXACT = 2, QK_ARITH_SQRTN = 3 };
 int qk_arith_evaluate(qk_ctx *ctx, qk_stream s, int what, int64_t n, const double *d_a, const double *d_b, double *d_out);
 
-/* ------------------------------------------------------------------ tracer particles (one level, one rank; qk_tracer.hip)
+/* ------------------------------------------------------------------ tracer particles (one level, one rank; qk_tracer.hip; refined levels: below)
  * Particles are structure-of-arrays in device memory owned by the caller: pos[d] / vel[d] (double; vel is the reference's rdata), d < ndim (the other
  * pointers are not read and may be NULL), id (int64), cpu (int32).
  * The plan maps a global cell index to its box in O(1): a dense lattice of box indices at the granularity of the common divisor of all box edges, for
@@ -740,6 +740,40 @@ int qk_tracer_AdvectWithUmac(qk_tracer_plan *plan, qk_stream s, const qk_array4 
  * keep[n] (one byte per particle) = 1 if the particle then lies in [plo, phi) in every direction, else 0 (AMReX invalidates a particle that left
  * through a non-periodic face; a NaN or infinite position is dropped as well).  Compacting the arrays by `keep` is the caller's. */
 int qk_tracer_Redistribute(qk_tracer_plan *plan, qk_stream s, int64_t np, double *const pos[3], unsigned char *keep);
+
+/* ------------------------------------------------------------------ tracer particles on a refined hierarchy (one rank; DESIGN.md §11 "refined levels")
+ * A plan for a level whose boxes need not tile the domain: lattice entries that no box covers hold -1.  Everything else as qk_tracer_plan_create
+ * (which keeps refusing such a level).  qk_tracer_AdvectWithUmac with a plan that has holes and no parent link: QK_ERR_UNSUPPORTED. */
+int qk_tracer_plan_create_refined(qk_level *lev, qk_tracer_plan **plan, const qk_geometry *geom, const double prob_lo[3], const double prob_hi[3],
+				  const double dx[3]);
+/* The parent link of a plan of level l, one per kind: the plan of level l - 1 (refinement ratio 2) that belongs to that kind's face arrays and
+ * the arrays themselves (tables as umac of qk_tracer_AdvectWithUmac, on the parent plan's level).  QK_TRACER_CUR: the parent's avgFaceVel of its
+ * current step with its current plan; QK_TRACER_PREV: that of its previous step with the plan (boxes) that step had — state_new_fc_ / state_old_fc_ of
+ * the reference (src/simulation.hpp:1896-1936, swapped at src/QuokkaSimulation.hpp:673).  The pointers are kept, not the data: they must stay valid
+ * until the link is replaced or cleared.  A face of kind K that the parent plan does not hold is looked up through the PARENT plan's own link of
+ * kind K, down to a plan without holes; at most QK_TRACER_MAX_DEPTH links deep. */
+enum { QK_TRACER_PREV = 0, QK_TRACER_CUR = 1, QK_TRACER_MAX_DEPTH = 3 };
+int qk_tracer_plan_set_parent(qk_tracer_plan *plan, int kind, qk_tracer_plan *parent, const qk_array4 *const parent_umac[3]);
+/* alpha, beta of G = alpha * U^prev + beta * U^cur, the parent's field at time + 0.5 dt_lev (FillPatchTwoLevels' GetData, reference
+ * src/simulation.hpp:1896-1936; the fill itself :1413, :1849-1852).  alpha == 0: U^cur alone; beta == 0: U^prev alone (its almostEqual short cuts). */
+int qk_tracer_plan_set_time_weights(qk_tracer_plan *plan, double alpha, double beta);
+int qk_tracer_plan_clear_parent(qk_tracer_plan *plan);
+/* With both links set, qk_tracer_AdvectWithUmac(plan, ...) reads a stencil face (i_0, i_1, i_2) of direction d — resolved against the level's own
+ * domain as above — that no box of the plan holds as
+ *   (1 - w) * G(c) + w * G(c + e_d),   c_e = floor(i_e / 2),   w = 0.5 * (i_d - 2 c_d)
+ * (AMReX's face_linear_interp at ratio 2: linear along the normal, piecewise constant across; evaluated in this form for even faces too), the
+ * parent's faces c, c + e_d resolved against the parent's domain; U^K(c) of a face the parent plan of kind K does not hold is the same expression
+ * on ITS parent's U^K.  A particle whose stencil faces are all held takes the arithmetic of the single-level kernel.  Two launches: the first
+ * moves every particle whose stencil is held in both passes and marks the others in a byte array of the plan, the second moves the marked ones. */
+/* Where particles belong on a hierarchy: ParticleContainer::Redistribute(lev_min, finest, ngrow)'s locate step  reference src/simulation.hpp:1254-1258, :1317-1329
+ * plans[0 .. nlevels - 1]: the levels' plans, level 0 without holes; level[n]: the level particle n is stored on.  Per particle:
+ *  (a) periodic shift and keep[n] exactly as qk_tracer_Redistribute (plans[0]'s prob_lo / prob_hi); a dropped particle gets new_level -1;
+ *  (b) its cell on level m: i_e = floor((x_e - plo_e) * dxi_e(m)), clamped to [0, N_e(m) - 1];
+ *  (c) ngrow > 0 and 0 <= level[n] < nlevels and a cell within ngrow cells (every direction, no periodic wrap) of its level-level[n] cell lies in a
+ *      box of that level: new_level = level[n];
+ *  (d) else the finest level in [lev_min, nlevels - 1] whose boxes hold its cell; if none, the finest level below lev_min that does. */
+int qk_tracer_Where(qk_tracer_plan *const plans[], int nlevels, qk_stream s, int lev_min, int ngrow, int64_t np, double *const pos[3],
+		    const int *level, int *new_level, unsigned char *keep);
 
 #ifdef __cplusplus
 }

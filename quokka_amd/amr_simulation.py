@@ -368,6 +368,50 @@ class AmrLevelSim(HydroSimulation):
         self._t_adv += dt_lev
         return ok
 
+    # --- tracer particles of the level (AmrSimulation.do_tracers; DESIGN.md §11 "refined levels")
+    def _check_tracers(self):
+        super()._check_tracers()
+        if self.tracers_on_fused_stages:
+            raise capi.QkError("tracers_on_fused_stages: not built for the levels of an AmrSimulation (its levels advect tracers on the "
+                               "reference-shaped operators)")
+
+    def _make_tracers(self, inherit: Optional["AmrLevelSim"] = None):
+        """the level's particle container and the face fields its children read: `_tr_cur` / `_tr_prev` = (plan, avgFaceVel arrays) of the
+        level's current and previous step.  inherit: the level object a regrid replaced — its fields, WITH its plan, stay what the children
+        (and this level's next rotation) see until this level has stepped.  A level without a predecessor starts from zero on its boxes."""
+        from .tracers import TracerParticles
+        self.do_tracers = 1
+        self._check_tracers()
+        self.tracers = TracerParticles(self, refined=self.ilev > 0)
+        if inherit is not None and getattr(inherit, "_tr_cur", None) is not None:
+            self._tr_cur, self._tr_prev = inherit._tr_cur, inherit._tr_prev
+        else:
+            self._tr_cur = (self.tracers.plan, self._zero_faces())
+            self._tr_prev = (self.tracers.plan, self._zero_faces())
+
+    def _zero_faces(self):
+        return [MultiFab(self.lev, 1, 0, facedir=d, fill=0.0) for d in range(self.geom.ndim)]
+
+    def _rotate_tracer_fields(self):
+        """prev <- cur at the start of the level's step, the plan with its arrays (state_old_fc_ / state_new_fc_ are swapped at reference
+        src/QuokkaSimulation.hpp:673); cur: arrays on the level's present boxes, written by _advect_tracers"""
+        plan = self.tracers.plan
+        spare = self._tr_prev
+        self._tr_prev = self._tr_cur
+        reuse = spare[0] is plan and spare[1] is not self._tr_prev[1]
+        self._tr_cur = (plan, spare[1] if reuse else self._zero_faces())
+
+    def _advect_tracers(self, time: float, dt_lev: float):
+        """reference src/QuokkaSimulation.hpp:1290-1314 on a level of the hierarchy: avgFaceVel becomes the level's `cur`; a refined level's
+        plan is linked to the parent chain with the time weights of time + 0.5 dt_lev (FillPatchTwoLevels, src/simulation.hpp:1413, :1896-1936)"""
+        amr, l = self.amr, self.ilev
+        for d in range(self.geom.ndim):
+            self._tr_cur[1][d].copy_from(self._avg_face_vel[d])
+        alpha, beta = (0.0, 1.0) if l == 0 else amr._link_tracer_chain(l, time + 0.5 * dt_lev)
+        if amr.on_tracer_advect is not None:
+            amr.on_tracer_advect(l, time, dt_lev, alpha, beta)
+        self.tracers.advect(self._tr_cur[1], dt_lev)
+
     def advance_level(self, time: float, dt_lev: float) -> bool:
         """advanceSingleTimestepAtLevel: state_new <- advance(state_old = previous state_new), with the retries of
         advanceHydroAtLevelWithRetries (reference src/QuokkaSimulation.hpp:885-990); every attempt restarts at `time`"""
@@ -382,11 +426,17 @@ class AmrLevelSim(HydroSimulation):
         fr_as_crse = amr.levels[l + 1].fluxreg if (amr.do_reflux and l < amr.finest_level) else None
         if fr_as_fine is not None:
             fr_as_fine.save()  # originalFineData (reference src/QuokkaSimulation.hpp:894-900)
+        tracer_snap = None
+        if self.do_tracers and self.tracers is not None:
+            self._rotate_tracer_fields()
+            tracer_snap = self.tracers.snapshot()  # every retry starts from them (reference src/QuokkaSimulation.hpp:902-909, :930-935)
         for retry_count in range(7):
             nsubsteps = 2 ** retry_count
             dt_step = dt_lev / nsubsteps
             if retry_count > 0:
                 self.counters["retries"] += 1
+                if tracer_snap is not None:
+                    self.tracers.restore(tracer_snap)
                 # the substeps of the failed attempt that succeeded have already been added to the registers: back to the pre-advance
                 # state, or Reflux would count them twice (reference src/QuokkaSimulation.hpp:919-929)
                 if fr_as_crse is not None:
@@ -665,7 +715,11 @@ class AmrSimulation:
         self.ErrorEst: Optional[Callable[["AmrSimulation", int, MultiFab], None]] = None  # (amr, lev, tags) -> sets tags on level lev
         self.initial_conditions: Optional[Callable] = None  # fn(geom_of_level) -> fn(i, j, k) -> conserved state on index grids
         self.static_fine_boxes: Optional[List[List[Box]]] = None  # [lev-1] -> boxes of level lev: fixed grids instead of ErrorEst
-        self.do_tracers = 0  # (reference src/simulation.hpp:398) tracer particles live on one unrefined level (quokka_amd/tracers.py): refused here
+        # tracer particles (reference src/simulation.hpp:398): set before setInitialConditions, which then gives every level its own container
+        # (AmrLevelSim.tracers), creates one particle per level-0 cell and redistributes them over the levels.  One rank, hydro levels, RK2.
+        self.do_tracers = 0
+        # (tests) called as (lev, time, dt_lev, alpha, beta) just before a level's particles are advected: tracer_fields() is then what the kernel reads
+        self.on_tracer_advect: Optional[Callable] = None
 
     @property
     def finest_level(self) -> int:
@@ -850,6 +904,132 @@ class AmrSimulation:
                     break
         for lev in range(self.finest_level - 1, -1, -1):
             self.AverageDownTo(lev)
+        if self.do_tracers:
+            self.InitTracerParticles()
+
+    # ------------------------------------------------------------------ tracer particles (DESIGN.md §11 "refined levels")
+    def _check_tracers(self):
+        if self.nranks > 1:
+            raise capi.QkError("do_tracers: tracer particles are built for one rank (nranks > 1: no particle exchange between ranks)")
+        if self.rad_traits is not None:
+            raise capi.QkError("do_tracers: tracer particles are built for the hydro levels of the AMR driver, not for RadAmrLevelSim (radiation)")
+        if self.integratorOrder_ != 2:
+            raise capi.QkError("do_tracers: tracer particles need integratorOrder_ = 2 (the RK2 average of the face velocities)")
+        if self.finest_level > capi.QK_TRACER_MAX_DEPTH:
+            raise capi.QkError(f"do_tracers: more than {capi.QK_TRACER_MAX_DEPTH} refined levels (QK_TRACER_MAX_DEPTH)")
+
+    def InitTracerParticles(self):
+        """InitOnePerCell(0.5, 0.5, 0.5) on level 0, then Redistribute() (reference src/simulation.hpp:1995-2003)"""
+        if not self.do_tracers:
+            raise capi.QkError("InitTracerParticles: do_tracers is 0")
+        self._check_tracers()
+        for L in self.levels:
+            L._make_tracers()
+        self.levels[0].tracers.init_one_per_cell()
+        self.RedistributeTracers(0, 0)
+
+    def _link_tracer_chain(self, lev: int, t: float):
+        """every plan of levels 1 .. lev is linked to the parent level's (plan, arrays) of both kinds; returns (alpha, beta) of level lev's parent at
+        time t, as FillPatchTwoLevels' GetData weighs its old and new data (reference src/simulation.hpp:1896-1936), with its short cuts"""
+        from .tracers import CUR, PREV
+        for m in range(1, lev + 1):
+            Lm, Lp = self.levels[m], self.levels[m - 1]
+            seen = []
+            for plan in (Lm.tracers.plan, Lm._tr_cur[0], Lm._tr_prev[0]):
+                if any(plan is q for q in seen):
+                    continue
+                seen.append(plan)
+                plan.set_parent(CUR, *Lp._tr_cur)
+                plan.set_parent(PREV, *Lp._tr_prev)
+        p = self.levels[lev - 1]
+        t0, t1 = p.t_old, p.t_new
+        eps = 1.0e-10 * max(abs(t1 - t0), 1.0e-300)
+        if abs(t - t1) <= eps or t1 == t0:
+            alpha, beta = 0.0, 1.0
+        elif abs(t - t0) <= eps:
+            alpha, beta = 1.0, 0.0
+        else:
+            alpha, beta = (t1 - t) / (t1 - t0), (t - t0) / (t1 - t0)
+        self.levels[lev].tracers.plan.set_time_weights(alpha, beta)
+        return alpha, beta
+
+    def tracer_fields(self, lev: int, kind: int):
+        """(boxes, face arrays) of a level's `cur` (kind 1) or `prev` (kind 0) field: inside on_tracer_advect, what the kernel is about to read"""
+        L = self.levels[lev]
+        plan, arrays = L._tr_cur if kind else L._tr_prev
+        return plan.boxes, arrays
+
+    def RedistributeTracers(self, lev_min: int = 0, ngrow: int = 0):
+        """ParticleContainer::Redistribute(lev_min, finest, ngrow) on one rank (reference src/simulation.hpp:1254-1258, :1317-1329): the kernel
+        says where every particle of the levels >= lev_min belongs (qk_tracer_Where); the move is masks and cat — survivors keep their order,
+        arrivals are appended, by source level."""
+        from .tracers import where
+        fin = self.finest_level
+        plans = [L.tracers.plan for L in self.levels]
+        verdicts = {}
+        for l in range(lev_min, fin + 1):
+            T = self.levels[l].tracers
+            n = T.num_particles
+            if n == 0:
+                continue
+            new, _keep = where(self.ctx, plans, lev_min, ngrow, T.pos, torch.full((n,), l, dtype=torch.int32, device=self.ctx.device))
+            counts = torch.bincount((new + 1).to(torch.int64), minlength=fin + 2).cpu()  # (one device -> host read per level)
+            if int(counts[l + 1]) != n:
+                verdicts[l] = (new, counts)
+        if not verdicts:
+            return
+        out = {}
+        for m in range(fin + 1):
+            Tm = self.levels[m].tracers
+            parts = []
+            if m in verdicts:
+                parts.append((Tm, verdicts[m][0] == m))
+            elif Tm.num_particles:
+                parts.append((Tm, None))
+            arrivals = [(self.levels[l].tracers, new == m) for l, (new, counts) in sorted(verdicts.items()) if l != m and int(counts[m + 1]) > 0]
+            if m not in verdicts and not arrivals:
+                continue
+            parts += arrivals
+            pick = lambda a, mask: a if mask is None else a[mask]
+            out[m] = ([torch.cat([pick(T.pos[d], k) for T, k in parts]) for d in range(Tm.ndim)] if parts else None,
+                      [torch.cat([pick(T.vel[d], k) for T, k in parts]) for d in range(Tm.ndim)] if parts else None,
+                      torch.cat([pick(T.id, k) for T, k in parts]) if parts else None, torch.cat([pick(T.cpu, k) for T, k in parts]) if parts else None)
+        for m, (pos, vel, ids, cpu) in out.items():
+            Tm = self.levels[m].tracers
+            if pos is None:
+                Tm._alloc(0)
+            else:
+                Tm.take(pos, vel, ids, cpu)
+
+    def _tracers_after_regrid(self, old_levels):
+        """containers and plans for the levels a regrid made or remade; the particles of a level that is gone wait on the finest level left for
+        the Redistribute that follows"""
+        for l, L in enumerate(self.levels):
+            if L.tracers is None:
+                old = old_levels[l] if l < len(old_levels) else None
+                L._make_tracers(inherit=old)
+                if old is not None and old.tracers is not None:
+                    L.tracers.take(old.tracers.pos, old.tracers.vel, old.tracers.id, old.tracers.cpu)
+        T = self.levels[-1].tracers
+        for old in old_levels[len(self.levels):]:
+            if old.tracers is not None and old.tracers.num_particles:
+                O = old.tracers
+                T.take([torch.cat([T.pos[d], O.pos[d]]) for d in range(T.ndim)], [torch.cat([T.vel[d], O.vel[d]]) for d in range(T.ndim)],
+                       torch.cat([T.id, O.id]), torch.cat([T.cpu, O.cpu]))
+
+    @property
+    def num_tracers(self) -> int:
+        return sum(L.tracers.num_particles for L in self.levels if L.tracers is not None)
+
+    def tracer_positions(self) -> np.ndarray:
+        """positions (np, 3) of all particles, level after level (the order of tracer_ids and tracer_levels)"""
+        return np.concatenate([L.tracers.positions() for L in self.levels], axis=0)
+
+    def tracer_ids(self) -> np.ndarray:
+        return np.concatenate([L.tracers.ids() for L in self.levels])
+
+    def tracer_levels(self) -> np.ndarray:
+        return np.concatenate([np.full(L.tracers.num_particles, l, dtype=np.int32) for l, L in enumerate(self.levels)])
 
     def _set_level_ic(self, lev: int):
         L = self.levels[lev]
@@ -948,6 +1128,8 @@ class AmrSimulation:
         its flux register, the cells it averages down to.  Required of every interpolation item: the coarse cells it reads lie in the VALID
         region of its coarse box or beyond a physical boundary (never in ghost cells another box fills — those wait for the far boxes)."""
         L = self.levels[lev]
+        if self.do_tracers:  # no children beside the far boxes, no speculative coarse step: the particles would need a rollback of their own
+            return None
         if not (self.overlap_children and lev == 0 and self.nranks == 1 and self.rad_traits is None and lev < self.finest_level and self.do_reflux
                 and L.use_fused and L.integratorOrder_ == 2 and L.speculate_stage2 and not L.strang_sources and L.lev.nboxes > 1):
             return None
@@ -1037,9 +1219,13 @@ class AmrSimulation:
             self.levels[l].link_to_parent(self.levels[l - 1])
         self.__dict__.pop("_split_cache", None)
 
-    def timeStepWithSubcycling(self, lev: int, time: float):
+    def timeStepWithSubcycling(self, lev: int, time: float, iteration: int = 1):
         if self.regrid_int > 0 and lev < self.max_level and self.istep[lev] > self.last_regrid_step[lev] and self.istep[lev] % self.regrid_int == 0:
+            before = list(self.levels)
             self.regrid(lev)
+            if self.do_tracers and self.static_fine_boxes is None:  # Redistribute(lev) after the regrid (reference src/simulation.hpp:1254-1258)
+                self._tracers_after_regrid(before)
+                self.RedistributeTracers(lev, 0)
             for k in range(lev, self.finest_level + 1):
                 self.last_regrid_step[k] = self.istep[k]
         L = self.levels[lev]
@@ -1059,7 +1245,7 @@ class AmrSimulation:
             self._spec_entries = [] if self.defer_child_verdicts else None
             try:
                 for i in range(2):
-                    self.timeStepWithSubcycling(lev + 1, time + i * self.dt_[lev + 1])
+                    self.timeStepWithSubcycling(lev + 1, time + i * self.dt_[lev + 1], i + 1)
                 entries = self._spec_entries
             finally:
                 L._children_beside_far_boxes = False
@@ -1110,17 +1296,25 @@ class AmrSimulation:
                     L._new_ghosts_filled = True
             for i in range(2):
                 if lev < self.finest_level:
-                    self.timeStepWithSubcycling(lev + 1, time + i * self.dt_[lev + 1])
+                    self.timeStepWithSubcycling(lev + 1, time + i * self.dt_[lev + 1], i + 1)
             if lev < self.finest_level:
                 if self.do_reflux:
                     L.reflux_from(self.levels[lev + 1])
                 self.AverageDownTo(lev)
                 L.FixupState()
                 L._new_ghosts_filled = False
+        # Redistribute(lev, finest, ngrow): ngrow = 0 on level 0, else the iteration; nsubsteps = 2 (reference src/simulation.hpp:1317-1329)
+        if self.do_tracers and (lev == 0 or iteration < 2):
+            self.RedistributeTracers(lev, 0 if lev == 0 else iteration)
 
     def step(self):
         if self.do_tracers:
-            raise capi.QkError("do_tracers: tracer particles are not built for the AMR driver (no Redistribute between levels); use HydroSimulation")
+            if not self.levels or self.levels[0].tracers is None:
+                raise capi.QkError("do_tracers: the AMR driver has no particles: setInitialConditions of the AMR driver creates them when do_tracers "
+                                   "is set before it (or call InitTracerParticles() after it)")
+            self._check_tracers()
+            for L in self.levels:
+                L._check_tracers()
         self.computeTimestep()
         self.timeStepWithSubcycling(0, self.tNew_)
         self.tNew_ += self.dt_[0]

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("QK_LIB_PATH", os.path.join(_HERE, "lib", "libquokka_a
 
 QK_OK, QK_ERR_INVALID, QK_ERR_HIP, QK_ERR_UNSUPPORTED, QK_ERR_STATE = 0, -1, -2, -3, -4
 ERR_UNSUPPORTED = QK_ERR_UNSUPPORTED
+QK_TRACER_PREV, QK_TRACER_CUR, QK_TRACER_MAX_DEPTH = 0, 1, 3  # include/quokka_amd.h
 HOOK_COMPILED = 100  # QK_HOOK_COMPILED: a hook that is the problem's own compiled device function (the library entry points refuse to evaluate it)
 DIR_X1, DIR_X2, DIR_X3 = 0, 1, 2
 ARITH_DIVBY_RECIPOF, ARITH_DIVN, ARITH_RECIPEXACT, ARITH_SQRTN = 0, 1, 2, 3  # qk_arith_evaluate
@@ -254,6 +255,11 @@ def lib() -> C.CDLL:
     L.qk_tracer_InitOnePerCell.argtypes = [vp, vp, cd * 3, vp * 3, vp * 3, vp, vp, C.c_int64, ci]
     L.qk_tracer_AdvectWithUmac.argtypes = [vp, vp, vp * 3, cd, C.c_int64, vp * 3, vp * 3]
     L.qk_tracer_Redistribute.argtypes = [vp, vp, C.c_int64, vp * 3, vp]
+    L.qk_tracer_plan_create_refined.argtypes = [vp, P(vp), P(Geometry), cd * 3, cd * 3, cd * 3]
+    L.qk_tracer_plan_set_parent.argtypes = [vp, ci, vp, vp * 3]
+    L.qk_tracer_plan_set_time_weights.argtypes = [vp, cd, cd]
+    L.qk_tracer_plan_clear_parent.argtypes = [vp]
+    L.qk_tracer_Where.argtypes = [P(vp), ci, vp, ci, ci, C.c_int64, vp * 3, vp, vp, vp]
     _lib = L
     return L
 
@@ -284,6 +290,7 @@ DECLARED_SYMBOLS = [
     "qk_fluxreg_create_crse_part", "qk_pcopy_plan_create", "qk_pcopy_plan_destroy", "qk_pcopy_plan_num_peers", "qk_pcopy_plan_peer", "qk_pcopy_plan_num_items",
     "qk_pcopy_plan_item", "qk_ParallelCopy_local", "qk_ParallelCopy_pack", "qk_ParallelCopy_unpack",
     "qk_tracer_plan_create", "qk_tracer_plan_destroy", "qk_tracer_plan_lattice", "qk_tracer_InitOnePerCell", "qk_tracer_AdvectWithUmac", "qk_tracer_Redistribute",
+    "qk_tracer_plan_create_refined", "qk_tracer_plan_set_parent", "qk_tracer_plan_set_time_weights", "qk_tracer_plan_clear_parent", "qk_tracer_Where",
 ]
 
 

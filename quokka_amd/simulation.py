@@ -380,9 +380,12 @@ class HydroSimulation:
         self.tracers.init_one_per_cell()
 
     def _check_tracers(self):
-        """what the tracer particles are built for: one plain hydro level on one rank, RK2"""
-        if type(self) is not HydroSimulation:
-            raise capi.QkError(f"do_tracers: tracer particles are built for HydroSimulation alone, not for {type(self).__name__} (AMR levels, radiation)")
+        """what the tracer particles are built for: one plain hydro level on one rank — a HydroSimulation, or a hydro level of an AmrSimulation
+        (AmrLevelSim, whose particles the AMR driver creates and redistributes) —, RK2"""
+        from .amr_simulation import AmrLevelSim  # (imports this module)
+        if type(self) is not HydroSimulation and type(self) is not AmrLevelSim:
+            raise capi.QkError(f"do_tracers: tracer particles are built for HydroSimulation and the hydro levels of AmrSimulation, not for "
+                               f"{type(self).__name__} (radiation)")
         if self.nranks > 1:
             raise capi.QkError("do_tracers: tracer particles are built for one rank (nranks > 1: no particle exchange between ranks)")
         if self.integratorOrder_ != 2:
@@ -953,12 +956,16 @@ class HydroSimulation:
             # on avgFaceVel of the stage-2 attempt that stood: the operators' (also a stage 2 redone on them) or the fused stage's own
             if self._avg_face_vel is None:
                 raise capi.QkError("do_tracers: no stage 2 of this advance left avgFaceVel behind")
-            self.tracers.advect(self._avg_face_vel, dt_lev)
+            self._advect_tracers(time, dt_lev)
         if self.strang_sources:
             ok = self._strang_sources(self.state_new_cc_, time + dt_lev, 0.5 * dt_lev)
             self._signal_of_state_new = None  # the sources changed the energies: the signal speeds FixupState left no longer describe the state
             return (not self.isCflViolated(dt_lev)) and ok
         return not self.isCflViolated(dt_lev)
+
+    def _advect_tracers(self, time: float, dt_lev: float):
+        """AdvectWithUmac on avgFaceVel of the stage 2 that stood; a level of a hierarchy links its parent's fields first (AmrLevelSim)"""
+        self.tracers.advect(self._avg_face_vel, dt_lev)
 
     def advanceHydroAtLevelWithRetries(self, dt_lev: float) -> bool:
         max_retries = 6

@@ -1,4 +1,4 @@
-"""Tracer particles of one level on one rank (reference src/simulation.hpp:398, :593, :1993-2005, :1317-1329; src/QuokkaSimulation.hpp:1290-1314):
+"""Tracer particles on one rank, per level (reference src/simulation.hpp:398, :593, :1993-2005, :1317-1329; src/QuokkaSimulation.hpp:1290-1314):
 one particle per cell, advected with the time-averaged face velocity of the RK2 step.
 
 Host plumbing only: the particle arrays are torch tensors (structure of arrays, as the C-ABI takes them), every particle is moved by the HIP kernels
@@ -20,20 +20,75 @@ def _d3(v: Sequence[float]):
     return (C.c_double * 3)(*[float(x) for x in (list(v) + [0.0, 0.0, 0.0])[:3]])
 
 
-class TracerParticles:
-    """amrex::TracerParticleContainer for a HydroSimulation: pos / vel (double, per direction), id (int64), cpu (int32) in device memory."""
+PREV, CUR = 0, 1  # QK_TRACER_PREV / QK_TRACER_CUR
 
-    def __init__(self, sim):
+
+class TracerPlan:
+    """qk_tracer_plan of one level: the cell -> box lattice and the geometry.  refined = True: the boxes need not tile the domain
+    (qk_tracer_plan_create_refined); AdvectWithUmac then needs the links to the parent level's plans and face arrays (set_parent)."""
+
+    def __init__(self, ctx, lev, geom, refined: bool = False, boxes=None):
+        self.ctx, self.lev, self.geom, self.refined = ctx, lev, geom, refined
+        self.boxes = [(list(lo), list(hi)) for lo, hi in boxes] if boxes is not None else None  # (host copy, for read-out)
+        self._geom_c = geom.c_struct()
+        h = C.c_void_p()
+        fn = ctx.L.qk_tracer_plan_create_refined if refined else ctx.L.qk_tracer_plan_create
+        ctx.check(fn(lev.h, C.byref(h), C.byref(self._geom_c), _d3(geom.prob_lo), _d3(geom.prob_hi), _d3(geom.dx)),
+                  "qk_tracer_plan_create_refined" if refined else "qk_tracer_plan_create")
+        self.h = h
+        self._linked = {}  # kind -> (parent plan, its face arrays): the library keeps their pointers, this keeps them alive
+
+    def set_parent(self, kind: int, parent: "TracerPlan", umac: Sequence[MultiFab]):
+        """the parent level's plan and face arrays of one kind (PREV: its previous step, with the boxes that step had; CUR: its current step)"""
+        nd = self.geom.ndim
+        for d in range(nd):
+            assert umac[d].facedir == d and umac[d].ncomp == 1 and umac[d].nghost == 0 and umac[d].level is parent.lev
+        tabs = (C.c_void_p * 3)(*[umac[d].ptr if d < nd else None for d in range(3)])
+        self.ctx.check(self.ctx.L.qk_tracer_plan_set_parent(self.h, int(kind), parent.h, tabs), "qk_tracer_plan_set_parent")
+        self._linked[kind] = (parent, list(umac[:nd]))
+
+    def set_time_weights(self, alpha: float, beta: float):
+        self.ctx.check(self.ctx.L.qk_tracer_plan_set_time_weights(self.h, float(alpha), float(beta)), "qk_tracer_plan_set_time_weights")
+
+    def clear_parent(self):
+        self.ctx.check(self.ctx.L.qk_tracer_plan_clear_parent(self.h), "qk_tracer_plan_clear_parent")
+        self._linked = {}
+
+    def __del__(self):
+        try:
+            self.ctx.L.qk_tracer_plan_destroy(self.h)
+        except Exception:
+            pass
+
+
+def where(ctx, plans: Sequence[TracerPlan], lev_min: int, ngrow: int, pos: Sequence[torch.Tensor], level: torch.Tensor):
+    """qk_tracer_Where: (new level per particle (int32, -1 = dropped), keep (bool)); `pos` is shifted in place in the periodic directions"""
+    n = int(level.numel())
+    new = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    keep = torch.empty(n, dtype=torch.bool, device=ctx.device)
+    if n == 0:
+        return new, keep
+    assert level.dtype == torch.int32 and level.is_contiguous()
+    hs = (C.c_void_p * len(plans))(*[p.h for p in plans])
+    ctx.check(ctx.L.qk_tracer_Where(hs, len(plans), ctx.stream(), int(lev_min), int(ngrow), n, TracerParticles._ptrs(pos), C.c_void_p(level.data_ptr()),
+                                    C.c_void_p(new.data_ptr()), C.c_void_p(keep.data_ptr())), "qk_tracer_Where")
+    return new, keep
+
+
+class TracerParticles:
+    """amrex::TracerParticleContainer for a HydroSimulation, or for one level of an AmrSimulation (refined = True: a TracerPlan whose boxes need
+    not tile the domain): pos / vel (double, per direction), id (int64), cpu (int32) in device memory."""
+
+    def __init__(self, sim, refined: bool = False):
         self.sim, self.ctx, self.lev, self.geom = sim, sim.ctx, sim.lev, sim.geom
         self.ndim = sim.geom.ndim
-        g = sim.geom
-        self._geom_c = g.c_struct()
-        h = C.c_void_p()
-        self.ctx.check(self.ctx.L.qk_tracer_plan_create(self.lev.h, C.byref(h), C.byref(self._geom_c), _d3(g.prob_lo), _d3(g.prob_hi), _d3(g.dx)),
-                       "qk_tracer_plan_create")
-        self.h = h
+        self.plan = TracerPlan(self.ctx, self.lev, self.geom, refined, getattr(sim, "my_boxes", None))
         self.last_keep = None
         self._alloc(0)
+
+    @property
+    def h(self):
+        return self.plan.h
 
     def _alloc(self, n: int):
         dev = self.ctx.device
@@ -125,8 +180,6 @@ class TracerParticles:
         self.id = torch.from_numpy(np.ascontiguousarray(i)).to(dev)
         self.cpu = torch.full((p.shape[0],), int(self.sim.rank), dtype=torch.int32, device=dev)
 
-    def __del__(self):
-        try:
-            self.ctx.L.qk_tracer_plan_destroy(self.h)
-        except Exception:
-            pass
+    def take(self, pos, vel, ids, cpu):
+        """take over device arrays as they are (the AMR driver's Redistribute)"""
+        self.pos, self.vel, self.id, self.cpu = list(pos), list(vel), ids, cpu
