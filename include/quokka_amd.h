@@ -37,7 +37,8 @@ typedef enum qk_status {
 	QK_ERR_INVALID = -1,	 /* bad argument (null pointer, unknown enum, mismatched sizes) */
 	QK_ERR_HIP = -2,	 /* a HIP runtime call failed; see qk_last_error() */
 	QK_ERR_UNSUPPORTED = -3, /* valid reference feature this build does not cover (e.g. mass scalars) */
-	QK_ERR_STATE = -4	 /* physical state error the reference treats as fatal (rho <= 0 in SyncDualEnergy) */
+	QK_ERR_STATE = -4,	 /* physical state error the reference treats as fatal (rho <= 0 in SyncDualEnergy) */
+	QK_ERR_NOT_CONVERGED = -5 /* an iterative solve did not reach its tolerance within max_iter (qk_gravity_dirichlet_solve) */
 } qk_status;
 
 /* == amrex::Array4<double> */
@@ -774,6 +775,37 @@ int qk_tracer_plan_clear_parent(qk_tracer_plan *plan);
  *  (d) else the finest level in [lev_min, nlevels - 1] whose boxes hold its cell; if none, the finest level below lev_min that does. */
 int qk_tracer_Where(qk_tracer_plan *const plans[], int nlevels, qk_stream s, int lev_min, int ngrow, int64_t np, double *const pos[3],
 		    const int *level, int *new_level, unsigned char *keep);
+
+/* ------------------------------------------------------------------ self-gravity (one level, one rank, 3-D, cubic cells; qk_gravity.hip)
+ * The reference solves lap(phi) = 4 pi G rho with open boundaries once per coarse step and kicks the state (src/simulation.hpp:1011-1095,
+ * src/QuokkaSimulation.hpp:709-757).  Its solver is amrex::OpenBCSolver; the discrete problem here is this project's definition.
+ * phi, f: DENSE device arrays of (n[0]+2)(n[1]+2)(n[2]+2) doubles, x fastest, cell (i, j, k) of the lattice [0, n) at (i+1) + (n[0]+2) * ((j+1) +
+ * (n[1]+2) * (k+1)); the ghost layer of phi holds the Dirichlet data at the centres of the face-adjacent ghost cells (edges and corners are never
+ * read).  n[d] even, 4 .. 4096, else QK_ERR_UNSUPPORTED.  The ghost list: the S = 2 (n1 n2 + n0 n2 + n0 n1) face-adjacent ghost cells in the order
+ * x-lo, x-hi, y-lo, y-hi, z-lo, z-hi, within a face the lower tangential direction fastest.  `scratch`: a device allocation of at least
+ * qk_gravity_scratch_bytes(n) bytes, shared by the calls that take one. */
+int64_t qk_gravity_scratch_bytes(const int n[3]); /* -1: n refused */
+int64_t qk_gravity_num_ghosts(const int n[3]);	  /* S; -1: n refused */
+/* f(cell) += 4.0 * M_PI * G * state(cell, density_comp) for every valid cell of the level's boxes (fillPoissonRhsAtLevel, QuokkaSimulation.hpp:709-722:
+ * "add", so that a particle deposit can precede it; the caller zeroes f).  lev->ndim != 3: QK_ERR_UNSUPPORTED. */
+int qk_gravity_fill_rhs(qk_level *lev, qk_stream s, double G, const qk_array4 *state, int density_comp, const int n[3], double *f);
+/* L phi = f, L u = sum_d (u(+e_d) - 2 u + u(-e_d)) / h^2, the ghost layer of phi as Dirichlet data, the interior of phi as the initial guess.
+ * Cell-centred geometric multigrid, V(2,2) cycles of red-black Gauss-Seidel; stops when max |f - L phi| <= max(reltol * max |f|, abstol * min f)
+ * (src/simulation.hpp:1057), checked before the first and after every cycle.  Not reached after max_iter cycles: QK_ERR_NOT_CONVERGED (phi holds the
+ * last iterate).  f not finite: QK_ERR_STATE.  *iters: cycles taken; *resnorm: the last max |f - L phi| (either may be NULL).  SYNCHRONOUS: the host
+ * reads the residual norm once per cycle. */
+int qk_gravity_dirichlet_solve(qk_ctx *ctx, qk_stream s, const int n[3], double h, const double *f, double *phi, double reltol, double abstol, int max_iter,
+			       void *scratch, int64_t scratch_bytes, int *iters, double *resnorm);
+/* James' method on the lattice.  gather: s_out[g] = phi(nb(g)), nb(g) the interior neighbour of ghost g.  potential: bc[g] = - sum_g' K(g - g') s_in[g']
+ * over all S ghosts (K: DESIGN.md §13; the offsets r^2 = 0 and 1 are decided on integers), the sources in list order, cut into parts whose partial
+ * sums are added in order: deterministic.  scatter: the ghost layer of phi <- bc. */
+int qk_gravity_surface_gather(qk_ctx *ctx, qk_stream s, const int n[3], const double *phi, double *s_out);
+int qk_gravity_surface_potential(qk_ctx *ctx, qk_stream s, const int n[3], const double *s_in, double *bc, void *scratch, int64_t scratch_bytes);
+int qk_gravity_surface_scatter(qk_ctx *ctx, qk_stream s, const int n[3], const double *bc, double *phi);
+/* applyPoissonGravityAtLevel (QuokkaSimulation.hpp:724-757) per valid cell, its operations in its order: g_d = -0.5 * (phi(+e_d) - phi(-e_d)) / dx[d];
+ * p_d += dt * rho * g_d; E += KE_new - KE_old, KE = 0.5 * (px^2 + py^2 + pz^2) / rho.  phi(+-e_d) is read from the dense array, the ghost layer on the
+ * domain faces.  dx not equal in all directions to 1e-12 relative, lev->ndim != 3: QK_ERR_UNSUPPORTED. */
+int qk_gravity_kick(qk_level *lev, qk_stream s, const int n[3], const double *phi, const double dx[3], double dt, const qk_array4 *state);
 
 #ifdef __cplusplus
 }

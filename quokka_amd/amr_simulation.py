@@ -718,6 +718,8 @@ class AmrSimulation:
         # tracer particles (reference src/simulation.hpp:398): set before setInitialConditions, which then gives every level its own container
         # (AmrLevelSim.tracers), creates one particle per level-0 cell and redistributes them over the levels.  One rank, hydro levels, RK2.
         self.do_tracers = 0
+        # self-gravity (reference src/simulation.hpp:1011-1095) is built for one level (HydroSimulation.doPoissonSolve_): refused by name here
+        self.doPoissonSolve_ = 0
         # (tests) called as (lev, time, dt_lev, alpha, beta) just before a level's particles are advected: tracer_fields() is then what the kernel reads
         self.on_tracer_advect: Optional[Callable] = None
 
@@ -882,6 +884,7 @@ class AmrSimulation:
     def setInitialConditions(self):
         """AmrCore::InitFromScratch: level 0, then finer levels from the tags of the initial conditions (MakeNewLevelFromScratch uses
         the problem's initial conditions on every level, reference src/simulation.hpp:1656-1702), then AverageDown"""
+        self._check_gravity()
         g0 = self.geom0
         self.levels = [self._make_level(0, self._chop(0, chop_domain(g0.n_cell, [self.max_grid_size] * 3)))]
         self._set_level_ic(0)
@@ -1307,7 +1310,13 @@ class AmrSimulation:
         if self.do_tracers and (lev == 0 or iteration < 2):
             self.RedistributeTracers(lev, 0 if lev == 0 else iteration)
 
+    def _check_gravity(self):
+        if self.doPoissonSolve_ or any(L.doPoissonSolve_ for L in getattr(self, "levels", [])):
+            raise capi.QkError("doPoissonSolve_: self-gravity is built for HydroSimulation (one level, hydro only), not for AmrSimulation and its "
+                               "levels (AmrLevelSim): no composite solve over a hierarchy")
+
     def step(self):
+        self._check_gravity()
         if self.do_tracers:
             if not self.levels or self.levels[0].tracers is None:
                 raise capi.QkError("do_tracers: the AMR driver has no particles: setInitialConditions of the AMR driver creates them when do_tracers "

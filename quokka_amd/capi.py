@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QK_LIB_PATH", os.path.join(_HERE, "lib", "libquokka_amd.so"))  # (override: A/B runs of two builds on one box)
 
-QK_OK, QK_ERR_INVALID, QK_ERR_HIP, QK_ERR_UNSUPPORTED, QK_ERR_STATE = 0, -1, -2, -3, -4
+QK_OK, QK_ERR_INVALID, QK_ERR_HIP, QK_ERR_UNSUPPORTED, QK_ERR_STATE, QK_ERR_NOT_CONVERGED = 0, -1, -2, -3, -4, -5
 ERR_UNSUPPORTED = QK_ERR_UNSUPPORTED
 QK_TRACER_PREV, QK_TRACER_CUR, QK_TRACER_MAX_DEPTH = 0, 1, 3  # include/quokka_amd.h
 HOOK_COMPILED = 100  # QK_HOOK_COMPILED: a hook that is the problem's own compiled device function (the library entry points refuse to evaluate it)
@@ -260,6 +260,18 @@ def lib() -> C.CDLL:
     L.qk_tracer_plan_set_time_weights.argtypes = [vp, cd, cd]
     L.qk_tracer_plan_clear_parent.argtypes = [vp]
     L.qk_tracer_Where.argtypes = [P(vp), ci, vp, ci, ci, C.c_int64, vp * 3, vp, vp, vp]
+    # self-gravity (csrc/qk_gravity.hip): no hasattr guard either
+    i3 = ci * 3
+    L.qk_gravity_scratch_bytes.argtypes = [i3]
+    L.qk_gravity_scratch_bytes.restype = C.c_int64
+    L.qk_gravity_num_ghosts.argtypes = [i3]
+    L.qk_gravity_num_ghosts.restype = C.c_int64
+    L.qk_gravity_fill_rhs.argtypes = [vp, vp, cd, vp, ci, i3, vp]
+    L.qk_gravity_dirichlet_solve.argtypes = [vp, vp, i3, cd, vp, vp, cd, cd, ci, vp, C.c_int64, P(ci), P(cd)]
+    L.qk_gravity_surface_gather.argtypes = [vp, vp, i3, vp, vp]
+    L.qk_gravity_surface_potential.argtypes = [vp, vp, i3, vp, vp, vp, C.c_int64]
+    L.qk_gravity_surface_scatter.argtypes = [vp, vp, i3, vp, vp]
+    L.qk_gravity_kick.argtypes = [vp, vp, i3, vp, cd * 3, cd, vp]
     _lib = L
     return L
 
@@ -291,6 +303,8 @@ DECLARED_SYMBOLS = [
     "qk_pcopy_plan_item", "qk_ParallelCopy_local", "qk_ParallelCopy_pack", "qk_ParallelCopy_unpack",
     "qk_tracer_plan_create", "qk_tracer_plan_destroy", "qk_tracer_plan_lattice", "qk_tracer_InitOnePerCell", "qk_tracer_AdvectWithUmac", "qk_tracer_Redistribute",
     "qk_tracer_plan_create_refined", "qk_tracer_plan_set_parent", "qk_tracer_plan_set_time_weights", "qk_tracer_plan_clear_parent", "qk_tracer_Where",
+    "qk_gravity_scratch_bytes", "qk_gravity_num_ghosts", "qk_gravity_fill_rhs", "qk_gravity_dirichlet_solve", "qk_gravity_surface_gather",
+    "qk_gravity_surface_potential", "qk_gravity_surface_scatter", "qk_gravity_kick",
 ]
 
 

@@ -245,6 +245,9 @@ class RadhydroSimulation(HydroSimulation):
 
     # advanceSingleTimestepAtLevel (reference src/QuokkaSimulation.hpp:653-707): hydro, then the radiation subcycle
     def step(self, dt: Optional[float] = None) -> bool:
+        if self.doPoissonSolve_:  # refused by name: self-gravity is built for a plain HydroSimulation (quokka_amd/gravity.py)
+            from . import gravity
+            gravity.check_supported(self)
         if dt is None:
             self.computeTimestep()
         else:

@@ -297,6 +297,16 @@ class HydroSimulation:
         # 1: a run with tracers keeps both RK stages on the fused kernels (use_fused), whose stage 2 then stores avgFaceVel itself
         # (qk_hydro_stage_args::store_vel_rk2; _tracers_on_fused).  0 (default): with tracers both stages take the reference-shaped operators.
         self.tracers_on_fused_stages = 0
+        # self-gravity (reference src/simulation.hpp:167-168, :392, :665, :883; quokka_amd/gravity.py): 1: an open-boundary Poisson solve
+        # after set_initial_conditions and after every step, then the kick by the full dt.  0 (default): nothing is allocated, nothing is launched.
+        self.doPoissonSolve_ = 0
+        self.Gconst_ = 6.67430e-8  # C::Gconst (cgs) of the reference's constants
+        self.reltolPoisson_ = 1.0e-5
+        self.abstolPoisson_ = 1.0e-5
+        self.do_cic_particles = 0  # (not built: refused by name together with doPoissonSolve_)
+        self.phi = None            # the dense potential (N2+2, N1+2, N0+2), ghost layer = boundary data; None until solved
+        self.poisson = None        # gravity.PoissonSolver, created by the first solve
+        self.on_gravity = None     # test hook: on_gravity(sim, dt) between the solve and the kick of ellipticSolveAllLevels
         self._avg_face_vel = None  # the face arrays that hold avgFaceVel of the stage-2 attempt that stood: set where a stage 2 is finished
         self.min_overlap_cells = 8 * 128 ** 3
         # the fused stage is instantiated for 0..3 passive scalars; mass scalars (consistent multi-fluid advection) take the operator path
@@ -368,6 +378,43 @@ class HydroSimulation:
         self.state_old_cc_.copy_from(self.state_new_cc_)
         if self.do_tracers:
             self.InitTracerParticles()
+        if self.doPoissonSolve_:
+            self.calculateGpotAllLevels()  # (reference src/simulation.hpp:665)
+
+    # ------------------------------------------------------------------ self-gravity
+    def calculateGpotAllLevels(self):
+        """phi from the density of state_new_cc_ (reference src/simulation.hpp:1011-1069): rhs = 0; rhs += 4 pi G rho; open-boundary solve to
+        max(reltolPoisson_ * max rhs, abstolPoisson_ * min rhs).  A solve that does not converge raises."""
+        if not self.doPoissonSolve_:
+            return
+        from . import gravity
+        gravity.check_supported(self)
+        if self.poisson is None:
+            self.poisson = gravity.PoissonSolver(self.ctx, self.geom.n_cell, self.geom.dx[0])
+        ps = self.poisson
+        ps.zero_rhs()
+        ps.fill_rhs(self.lev, self.state_new_cc_, self.Gconst_, 0)
+        ps.solve_open(self.reltolPoisson_, self.abstolPoisson_)
+        self.phi = ps.phi
+
+    def gravAccelAllLevels(self, dt: float):
+        """the operator-split kick of state_new_cc_ (reference src/simulation.hpp:1071-1084, src/QuokkaSimulation.hpp:724-757)"""
+        if not self.doPoissonSolve_:
+            return
+        if self.phi is None:
+            raise capi.QkError("gravAccelAllLevels: no potential (calculateGpotAllLevels has not run)")
+        self.poisson.kick(self.lev, self.state_new_cc_, self.geom.dx, dt)
+        # the kick changed momenta and energy of state_new_cc_: whatever the last stage or FixupState left about it (CFL maxima) is stale
+        self._signal_of_state_new = None
+
+    def ellipticSolveAllLevels(self, dt: float):
+        """reference src/simulation.hpp:1086-1096"""
+        if not self.doPoissonSolve_:
+            return
+        self.calculateGpotAllLevels()
+        if self.on_gravity is not None:
+            self.on_gravity(self, dt)
+        self.gravAccelAllLevels(dt)
 
     def InitTracerParticles(self):
         """one tracer per valid cell, at the cell centre: InitOnePerCell(0.5, 0.5, 0.5) (reference src/simulation.hpp:1993-2005).  Called by
@@ -1010,6 +1057,8 @@ class HydroSimulation:
         ok = self.advanceHydroAtLevelWithRetries(self.dt_)
         if self.do_tracers and self.tracers is not None:
             self.tracers.redistribute()  # Redistribute(lev, lev, ngrow = 0) on level 0 (reference src/simulation.hpp:1317-1329)
+        if self.doPoissonSolve_:
+            self.ellipticSolveAllLevels(self.dt_)  # (reference src/simulation.hpp:883)
         self.istep += 1
         self.cellUpdates_ += self.CountCells()
         return ok
