@@ -101,6 +101,139 @@ void orc_compute_hydro_fluxes(orc_hydro_traits const *t, int order, double K_vis
 	}
 }
 
+// ------------------------------------------------------------------ the hydro operators on arrays the caller owns (tests/test_hydro_cells_*.py)
+// Thin wrappers: boxes and layouts as orc_cons_to_prim.  `v` is the valid box, `g` the box the cell-centred state arrays live on.
+
+// ComputeFluxes<RIEMANN, DIR> (hydro_system.hpp:852-1112) on left / right states and primitives the caller supplies: L, R, flux (nvar components)
+// and fvel (one) live on the face box of v in direction dir, prim on v grown by nghost_prim >= 1 in the first ndim directions (it only supplies
+// the velocity differences du, dvl, dvr, dwl, dwr).  Every face is an independent sample.
+void orc_hydro_face_fluxes(orc_hydro_traits const *t, int riemann, int dir, double K_visc, double const *L, double const *R, double const *prim,
+			   int const vlo[3], int const vhi[3], int nghost_prim, double *flux, double *fvel)
+{
+	g_spacedim = t->ndim;
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	Box const f = faceBox(v, dir);
+	Box const g = grow(v, nghost_prim, t->ndim);
+	int const nv = h.tr.nvar();
+	h.ComputeFluxes(riemann, dir, Array4<double>(flux, f, nv), Array4<double>(fvel, f, 1), Array4<const double>(L, f, nv), Array4<const double>(R, f, nv),
+			Array4<const double>(prim, g, nv), K_visc, f);
+}
+
+// EnforceLimits (hydro_system.hpp:696-773) on the cells of v; the first nmscalars passive scalars are partial densities
+void orc_hydro_enforce_limits(orc_hydro_traits const *t, int nmscalars, double densityFloor, double tempFloor, double *state, int const glo[3], int const ghi[3],
+			      int const vlo[3], int const vhi[3])
+{
+	HydroSystem h = makeSystem(t);
+	h.tr.nmscalars = nmscalars;
+	h.EnforceLimits(densityFloor, tempFloor, Array4<double>(state, mkbox(glo, ghi), h.tr.nvar()), mkbox(vlo, vhi));
+}
+
+// SyncDualEnergy (hydro_system.hpp:816-850) on the cells of v.  A cell with rho <= 0 is fatal in the reference (amrex::Abort): here it is left
+// untouched and fatal (on v, one int per cell) is set for it; returns the number of such cells.
+long orc_hydro_sync_dual_energy(orc_hydro_traits const *t, double *state, int const glo[3], int const ghi[3], int const vlo[3], int const vhi[3], int *fatal)
+{
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	Array4<double> const U(state, mkbox(glo, ghi), h.tr.nvar());
+	Array4<int> const bad(fatal, v, 1);
+	long count = 0;
+	for (int k = v.lo[2]; k <= v.hi[2]; ++k) {
+		for (int j = v.lo[1]; j <= v.hi[1]; ++j) {
+			for (int i = v.lo[0]; i <= v.hi[0]; ++i) {
+				if (U(i, j, k, density_index) <= 0.) {
+					bad(i, j, k) = 1;
+					++count;
+					continue;
+				}
+				bad(i, j, k) = 0;
+				Box one;
+				one.lo[0] = one.hi[0] = i;
+				one.lo[1] = one.hi[1] = j;
+				one.lo[2] = one.hi[2] = k;
+				h.SyncDualEnergy(U, one);
+			}
+		}
+	}
+	return count;
+}
+
+// ComputeMaxSignalSpeed (hydro_system.hpp:223-252): maxSignal on v, one component
+void orc_hydro_max_signal_speed(orc_hydro_traits const *t, double const *cons, int const glo[3], int const ghi[3], int const vlo[3], int const vhi[3],
+				double *maxSignal)
+{
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	h.ComputeMaxSignalSpeed(Array4<const double>(cons, mkbox(glo, ghi), h.tr.nvar()), Array4<double>(maxSignal, v, 1), v);
+}
+
+// the serial reduction over v.  which = 0: maxSignalSpeedLocal (hydro_system.hpp:198-221); which = 1: the maximum of ComputeMaxSignalSpeed,
+// reduced the same way (result = std::max(result, value) from -infinity: a NaN value never replaces the result).
+double orc_hydro_max_signal_local(orc_hydro_traits const *t, int which, double const *cons, int const glo[3], int const ghi[3], int const vlo[3],
+				  int const vhi[3])
+{
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	Array4<const double> const U(cons, mkbox(glo, ghi), h.tr.nvar());
+	if (which == 0) {
+		return h.maxSignalSpeedLocal(U, v);
+	}
+	Fab<double> sig(v, 1);
+	h.ComputeMaxSignalSpeed(U, sig.array(), v);
+	double result = -std::numeric_limits<double>::infinity();
+	for (double const s : sig.d) {
+		result = std::max(result, s);
+	}
+	return result;
+}
+
+// PredictStep (hydro_system.hpp:475-497) with isStateValid (:423-446): consOld / consNew on g (ncomp components), rhs (nvars components) and
+// redoFlag on v; returns the number of flagged cells.  The reference always passes nvars = nvar_; with fewer the scalars of consNew are not this
+// call's product and the mass-scalar part of isStateValid does not apply (the rule of qk_hydro_PredictStep, include/quokka_amd.h).
+long orc_hydro_predict_step(orc_hydro_traits const *t, int nmscalars, double const *consOld, double *consNew, int ncomp, double const *rhs, double dt, int nvars,
+			    int const glo[3], int const ghi[3], int const vlo[3], int const vhi[3], int *redoFlag)
+{
+	HydroSystem h = makeSystem(t);
+	h.tr.nmscalars = (nvars >= kNumHydroVars + nmscalars) ? nmscalars : 0;
+	Box const v = mkbox(vlo, vhi);
+	Box const g = mkbox(glo, ghi);
+	h.PredictStep(Array4<const double>(consOld, g, ncomp), Array4<double>(consNew, g, ncomp), Array4<const double>(rhs, v, nvars), dt, nvars,
+		      Array4<int>(redoFlag, v, 1), v);
+	long count = 0;
+	for (int64_t n = 0; n < v.numPts(); ++n) {
+		count += (redoFlag[n] != redo_none) ? 1 : 0;
+	}
+	return count;
+}
+
+// ComputeRhsFromFluxes (hydro_system.hpp:448-473): rhs on v, flux[d] on the face box of v in direction d, nvars components each
+void orc_hydro_rhs_from_fluxes(orc_hydro_traits const *t, double *rhs, double const *const flux[3], double const dx[3], int nvars, int const vlo[3],
+			       int const vhi[3])
+{
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	std::array<Array4<const double>, 3> f{};
+	for (int d = 0; d < t->ndim; ++d) {
+		f[d] = Array4<const double>(flux[d], faceBox(v, d), nvars);
+	}
+	h.ComputeRhsFromFluxes(Array4<double>(rhs, v, nvars), f, dx, nvars, v);
+}
+
+// AddInternalEnergyPdV (hydro_system.hpp:775-814): rhs (ncomp_rhs components) and redoFlag on v, cons on g (>= 1 ghost cell: a flagged cell reads
+// its neighbours' velocities), vel[d] on the face box of v in direction d
+void orc_hydro_add_pdv(orc_hydro_traits const *t, double *rhs, int ncomp_rhs, double const *cons, int const glo[3], int const ghi[3], double const dx[3],
+		       double const *const vel[3], int const *redoFlag, int const vlo[3], int const vhi[3])
+{
+	HydroSystem const h = makeSystem(t);
+	Box const v = mkbox(vlo, vhi);
+	std::array<Array4<const double>, 3> f{};
+	for (int d = 0; d < t->ndim; ++d) {
+		f[d] = Array4<const double>(vel[d], faceBox(v, d), 1);
+	}
+	h.AddInternalEnergyPdV(Array4<double>(rhs, v, ncomp_rhs), Array4<const double>(cons, mkbox(glo, ghi), h.tr.nvar()), dx, f,
+			       Array4<const int>(redoFlag, v, 1), v);
+}
+
 // ------------------------------------------------------------------ multigroup helper functions (unit checks against independent formulas)
 double orc_planck_integral(double x) { return planck::integrate_planck_from_0_to_x(x); }
 double orc_planck_table_entry(int j) { return planck::Y_interp[j]; }

@@ -366,6 +366,109 @@ class Oracle:
                                           _dp(fl[0]), _dp(fl[1]), _dp(fl[2]), _dp(fv[0]), _dp(fv[1]), _dp(fv[2]))
         return fl[: t.ndim], fv[: t.ndim]
 
+    # ---------------------------------------------------------------- hydro operators on arrays the caller owns
+    # v = (vlo, vhi) is the valid box; cell-centred state arrays live on v grown by `nghost` in the first t.ndim directions
+    @staticmethod
+    def _grown(t: HydroTraits, vlo, vhi, ng):
+        return [int(vlo[d]) - (ng if d < t.ndim else 0) for d in range(3)], [int(vhi[d]) + (ng if d < t.ndim else 0) for d in range(3)]
+
+    @staticmethod
+    def _shape(lo, hi, facedir=-1):
+        return tuple(int(hi[d] - lo[d] + 1 + (1 if d == facedir else 0)) for d in (2, 1, 0))
+
+    def hydro_face_fluxes(self, t: HydroTraits, riemann: int, d: int, L: np.ndarray, R: np.ndarray, prim: np.ndarray, vlo, vhi, nghost_prim=1, K_visc=0.0):
+        """ComputeFluxes<riemann, d> on caller-supplied left / right states (face box of v, nvar components) and primitives (v grown by
+        nghost_prim, the velocity differences only): returns (flux, face velocity) on the face box"""
+        nv = 6 + t.nscalars
+        fs = self._shape(vlo, vhi, d)
+        assert L.shape == R.shape == (nv,) + fs and prim.shape == (nv,) + self._shape(*self._grown(t, vlo, vhi, nghost_prim)) and nghost_prim >= 1
+        flux, fvel = np.empty((nv,) + fs), np.empty(fs)
+        f = self.lib.orc_hydro_face_fluxes
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, _I3, _I3, C.c_int, C.c_void_p,
+                                 C.c_void_p], None
+        f(C.byref(t), int(riemann), int(d), float(K_visc), _dp(L), _dp(R), _dp(prim), _i3(vlo), _i3(vhi), int(nghost_prim), _dp(flux), _dp(fvel))
+        return flux, fvel
+
+    def hydro_enforce_limits(self, t: HydroTraits, state: np.ndarray, vlo, vhi, nghost, density_floor: float, temp_floor: float, nmscalars=0) -> np.ndarray:
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        out = np.array(state, dtype=np.float64, order="C")
+        assert out.shape == (6 + t.nscalars,) + self._shape(glo, ghi)
+        f = self.lib.orc_hydro_enforce_limits
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_int, C.c_double, C.c_double, C.c_void_p, _I3, _I3, _I3, _I3], None
+        f(C.byref(t), int(nmscalars), float(density_floor), float(temp_floor), _dp(out), _i3(glo), _i3(ghi), _i3(vlo), _i3(vhi))
+        return out
+
+    def hydro_sync_dual_energy(self, t: HydroTraits, state: np.ndarray, vlo, vhi, nghost):
+        """returns (state, fatal): fatal (bool, on v) marks the cells the reference aborts on (rho <= 0); they are left untouched"""
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        out = np.array(state, dtype=np.float64, order="C")
+        assert out.shape == (6 + t.nscalars,) + self._shape(glo, ghi)
+        fatal = np.zeros(self._shape(vlo, vhi), dtype=np.int32)
+        f = self.lib.orc_hydro_sync_dual_energy
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_void_p, _I3, _I3, _I3, _I3, C.c_void_p], C.c_long
+        n = f(C.byref(t), _dp(out), _i3(glo), _i3(ghi), _i3(vlo), _i3(vhi), fatal.ctypes.data_as(C.c_void_p))
+        assert n == int(fatal.sum())
+        return out, fatal.astype(bool)
+
+    def hydro_max_signal_speed(self, t: HydroTraits, cons: np.ndarray, vlo, vhi, nghost) -> np.ndarray:
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        assert cons.shape == (6 + t.nscalars,) + self._shape(glo, ghi)
+        out = np.empty(self._shape(vlo, vhi))
+        f = self.lib.orc_hydro_max_signal_speed
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_void_p, _I3, _I3, _I3, _I3, C.c_void_p], None
+        f(C.byref(t), _dp(cons), _i3(glo), _i3(ghi), _i3(vlo), _i3(vhi), _dp(out))
+        return out
+
+    def hydro_max_signal_local(self, t: HydroTraits, which: int, cons: np.ndarray, vlo, vhi, nghost) -> float:
+        """the serial reduction over v: which = 0 maxSignalSpeedLocal, which = 1 the maximum of ComputeMaxSignalSpeed (a NaN never wins)"""
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        assert cons.shape == (6 + t.nscalars,) + self._shape(glo, ghi)
+        f = self.lib.orc_hydro_max_signal_local
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_int, C.c_void_p, _I3, _I3, _I3, _I3], C.c_double
+        return float(f(C.byref(t), int(which), _dp(cons), _i3(glo), _i3(ghi), _i3(vlo), _i3(vhi)))
+
+    def hydro_predict_step(self, t: HydroTraits, cons_old: np.ndarray, cons_new: np.ndarray, rhs: np.ndarray, dt: float, nvars: int, vlo, vhi, nghost,
+                           nmscalars=0):
+        """PredictStep + isStateValid: returns (new state, redo flags on v, number of flagged cells); cons_new supplies what the call leaves alone"""
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        out = np.array(cons_new, dtype=np.float64, order="C")
+        assert cons_old.shape == out.shape == (out.shape[0],) + self._shape(glo, ghi) and rhs.shape == (nvars,) + self._shape(vlo, vhi)
+        flags = np.full(self._shape(vlo, vhi), -1, dtype=np.int32)
+        f = self.lib.orc_hydro_predict_step
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, _I3, _I3, _I3, _I3,
+                                 C.c_void_p], C.c_long
+        n = f(C.byref(t), int(nmscalars), _dp(cons_old), _dp(out), out.shape[0], _dp(rhs), float(dt), int(nvars), _i3(glo), _i3(ghi), _i3(vlo), _i3(vhi),
+              flags.ctypes.data_as(C.c_void_p))
+        return out, flags, int(n)
+
+    def hydro_rhs_from_fluxes(self, t: HydroTraits, fluxes, dx, nvars: int, vlo, vhi) -> np.ndarray:
+        for d in range(t.ndim):
+            assert fluxes[d].shape == (nvars,) + self._shape(vlo, vhi, d)
+        rhs = np.empty((nvars,) + self._shape(vlo, vhi))
+        ptrs = (C.c_void_p * 3)(*[fluxes[d].ctypes.data if d < t.ndim else None for d in range(3)])
+        for d in range(t.ndim):
+            _dp(fluxes[d])
+        f = self.lib.orc_hydro_rhs_from_fluxes
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_void_p, C.c_void_p * 3, C.c_double * 3, C.c_int, _I3, _I3], None
+        f(C.byref(t), _dp(rhs), ptrs, (C.c_double * 3)(*[float(x) for x in dx]), int(nvars), _i3(vlo), _i3(vhi))
+        return rhs
+
+    def hydro_add_pdv(self, t: HydroTraits, rhs: np.ndarray, cons: np.ndarray, dx, vels, redo: np.ndarray, vlo, vhi, nghost) -> np.ndarray:
+        """AddInternalEnergyPdV: rhs (on v) + the -P div(v) term, div(v) from the face velocities (redo == 0) or from the cell velocities"""
+        glo, ghi = self._grown(t, vlo, vhi, nghost)
+        out = np.array(rhs, dtype=np.float64, order="C")
+        assert nghost >= 1 and cons.shape == (6 + t.nscalars,) + self._shape(glo, ghi) and out.shape[1:] == self._shape(vlo, vhi) == redo.shape
+        assert redo.dtype == np.int32 and redo.flags["C_CONTIGUOUS"]
+        for d in range(t.ndim):
+            assert vels[d].shape == self._shape(vlo, vhi, d)
+            _dp(vels[d])
+        ptrs = (C.c_void_p * 3)(*[vels[d].ctypes.data if d < t.ndim else None for d in range(3)])
+        f = self.lib.orc_hydro_add_pdv
+        f.argtypes, f.restype = [C.POINTER(HydroTraits), C.c_void_p, C.c_int, C.c_void_p, _I3, _I3, C.c_double * 3, C.c_void_p * 3, C.c_void_p, _I3, _I3], None
+        f(C.byref(t), _dp(out), out.shape[0], _dp(cons), _i3(glo), _i3(ghi), (C.c_double * 3)(*[float(x) for x in dx]), ptrs,
+          redo.ctypes.data_as(C.c_void_p), _i3(vlo), _i3(vhi))
+        return out
+
     # ---------------------------------------------------------------- whole simulation
     def average_down(self, fine: np.ndarray, flo, crse: np.ndarray, clo, region, scomp: int, ncomp: int, ratio=(2, 2, 2)):
         """amrex::average_down restated: fine / crse are (ncomp_total, nz, ny, nx) float64 arrays whose lower corners are flo / clo;

@@ -187,7 +187,58 @@ def test_fused_stage_with_artificial_viscosity_equals_operators(ctx, order):
     _fused_vs_operators(ctx, order, False, False, 0.1)
 
 
-def _fused_vs_operators(ctx, order, reconstruct_eint, isothermal, K_visc):
+@pytest.mark.parametrize("order,reconstruct_eint,isothermal",
+                         [(o, r, i) for i in (False, True) for r in (False, True) for o in (3, 2, 1) if not (i and r)])
+def test_fused_stage_equals_operators_on_a_state_that_takes_every_fan(ctx, order, reconstruct_eint, isothermal):
+    """the same comparison on fan_state (tests/hydro_cells_reference.py): random_state plus a rotating bulk velocity of a few c_s, so that both
+    supersonic fans and both star fans occur in every direction (asserted on the CPU: tests/test_hydro_cells_reference.py)"""
+    _fused_vs_operators(ctx, order, reconstruct_eint, isothermal, 0.0, state="fans")
+
+
+@pytest.mark.parametrize("order", [3, 1])
+def test_fused_stage_with_artificial_viscosity_equals_operators_on_a_state_that_takes_every_fan(ctx, order):
+    _fused_vs_operators(ctx, order, False, False, 0.1, state="fans")
+
+
+def test_fused_stage_on_a_state_that_takes_every_fan_matches_the_oracle(ctx, oracle):
+    """The fused stage against the oracle itself, not against the operators: fan_state loaded into both, the geometry of _fused_vs_operators
+    (32 x 24 x 16, two boxes, periodic), two advances of a fixed dt, every bit of the state.  Gamma law (the simulation oracle has no 3-D
+    isothermal set-up).  No flux correction and no retry on either side."""
+    import hydro_cells_reference as H
+    from quokka_amd import capi
+    from quokka_amd.simulation import Geometry, HydroSimulation
+    from test_hydro_ops_gpu import random_state
+    N = (32, 24, 16)
+    U0 = H.fan_state(random_state(np.random.default_rng(7), (N[2], N[1], N[0])))
+    so = oracle.sim(SEDOV, 3, list(N), [0.0] * 3, [1.0, 0.75, 0.5], [1, 1, 1], max_grid_size=[16, 24, 16])
+    geom = Geometry(3, list(N), [0.0] * 3, [1.0, 0.75, 0.5], [1, 1, 1])
+    bcs = [([capi.BC_INT_DIR] * 3, [capi.BC_INT_DIR] * 3)] * 6
+    sg = HydroSimulation(ctx, geom, capi.traits(1.4, False, 3), bcs, [16, 24, 16], use_fused=True)
+    sg.reconstructionOrder_ = 3
+    assert sg.use_fused and so.nboxes == sg.lev.nboxes == 2
+    ng = so.nghost
+    pad = H.periodic_pad(U0, ng)
+    for b in range(so.nboxes):
+        lo, hi = so.box(b)
+        assert (list(lo), list(hi)) == (list(sg.my_boxes[b][0]), list(sg.my_boxes[b][1]))
+        fab = np.ascontiguousarray(pad[:, lo[2]:hi[2] + 1 + 2 * ng, lo[1]:hi[1] + 1 + 2 * ng, lo[0]:hi[0] + 1 + 2 * ng])
+        so.set_state(fab, b, 0)
+        sg.state_new_cc_.set_fab(b, fab)
+    sg._signal_of_state_new = None
+    dt = 2.0e-4
+    for it in range(2):
+        assert so.advance_fixed_dt(dt) and sg.step(dt), it
+    co = so.counters()
+    assert co["fofc1_cells"] == co["fofc2_cells"] == co["retries"] == 0, co
+    assert sg.counters["fofc1_stages"] == sg.counters["fofc2_stages"] == sg.counters["retries"] == 0
+    for b in range(so.nboxes):
+        got, want = sg.state_new_cc_.valid(b).cpu().numpy(), so.valid(b)
+        assert np.isfinite(want).all() and not np.array_equal(want, U0[:, so.box(b)[0][2]:so.box(b)[1][2] + 1, so.box(b)[0][1]:so.box(b)[1][1] + 1,
+                                                                        so.box(b)[0][0]:so.box(b)[1][0] + 1])
+        assert np.array_equal(got, want), f"box {b}: {int((got != want).sum())} values differ, max abs diff {np.abs(got - want).max()}"
+
+
+def _fused_vs_operators(ctx, order, reconstruct_eint, isothermal, K_visc, state="random"):
     """Every template combination of the fused stage kernels (reconstruction order x reconstruct_eint x gamma-law /
     isothermal) against the reference-shaped operator chain — which tests/test_hydro_ops_gpu.py pins to the oracle — on a
     random shocked state, two boxes, periodic: both RK stages, new state, stage-1 face fluxes and redo flags bit for bit."""
@@ -203,6 +254,9 @@ def _fused_vs_operators(ctx, order, reconstruct_eint, isothermal, K_visc):
     bcs = [([capi.BC_INT_DIR] * 3, [capi.BC_INT_DIR] * 3)] * 6
     rng = np.random.default_rng(7)
     U0 = random_state(rng, (N[2], N[1], N[0]))
+    if state == "fans":
+        import hydro_cells_reference as H
+        U0 = H.fan_state(U0)
 
     def run(fused):
         sim = HydroSimulation(ctx, geom, tr, bcs, [16, 24, 16], use_fused=fused)
