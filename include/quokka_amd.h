@@ -202,6 +202,7 @@ int qk_advect_AddFluxesRK2(qk_level *lev, qk_stream s, qk_array4 *U_new, const q
 			   const double dx[3], int nvars);
 
 /* ------------------------------------------------------------------ fused fast path (MI355X design; same results) */
+#define QK_GHOST_FROM_SOURCE_ON 0x51475331 /* qk_hydro_stage_args::ghost_from_source */
 typedef struct qk_hydro_stage_args {
 	/* inputs */
 	const qk_array4 *U_in;	 /* ghost-filled state the fluxes are evaluated on (stage 1: U^n, stage 2: U^1) */
@@ -273,6 +274,17 @@ typedef struct qk_hydro_stage_args {
 				  * rk2_carry_rhs (the carried form has no halfVel) and in stage 1.  0: velRk2 is neither read nor required. */
 	qk_array4 *velRk2[3];	 /* face-centred like halfVel, 1 component, no ghost faces; required for d < ndim when store_vel_rk2 != 0.  Separate from
 				  * halfVel for the reason fluxRk2 is separate from halfFlux: both evaluations of a tile-boundary face need v1 intact */
+	int ghost_from_source;	 /* 0 (and every value but the one below): the ghost cells of U_in are filled (qk_FillBoundary_* + qk_FillPhysicalBoundary).
+				  * QK_GHOST_FROM_SOURCE_ON — a fixed pattern, not 1: this field was appended to the struct, a caller compiled against an
+				  * earlier header hands over a shorter one, and whatever lies behind it must not switch the feature on —: they are NOT — the pre-pass, the
+				  * fused XY sweep (its y march and the cells beside the box's first and last column in its wave-edge batch) and the Z sweep
+				  * read every cell outside a box from the valid cell the fill would have copied, with the sign the fill would have given it
+				  * (qk_ghost_source_plan below): same values, bit for bit, and no ghost-fill pass over memory.  The level must qualify
+				  * (qk_ghost_source_plan), the stage must be the carried form (rk2_carry_rhs) of a 3-D level without flux mask and passive
+				  * scalars on the fused XY sweep (QK_FUSEX != 0), U_in and U_out must be different arrays (a box reads its neighbours' valid
+				  * cells while they write theirs), and the arrays of the level's boxes must share their strides (they do wherever equal boxes
+				  * are allocated alike).  Nobody writes a ghost cell: a caller that skips its fills keeps track of that (the hosts'
+				  * "ghost cells stale" mark) and fills before anything else reads them. */
 } qk_hydro_stage_args;
 
 /* One RK stage of advanceHydroAtLevel (reference src/QuokkaSimulation.hpp:1099-1198 / 1202-1287) WITHOUT the
@@ -508,6 +520,23 @@ int qk_ghost_plan_box_is_remote(qk_ghost_plan *plan, int local_box); /* 1 / 0, <
 int qk_ghost_plan_set_box_remote(qk_ghost_plan *plan, int local_box, int flag);
 int qk_FillPhysicalBoundary_subset(qk_ghost_plan *plan, qk_stream s, qk_array4 *state, const qk_bcrec *bcs, const qk_dirichlet_face *dirichlet,
 				   int which);
+
+/* The source map of out-of-box cells (qk_hydro_stage_args::ghost_from_source).  On a level that QUALIFIES, what the fill above leaves in a ghost
+ * cell is the value of exactly one valid cell — the neighbouring box's, the box's own mirrored cell at a reflecting wall, its own clamped cell at
+ * an extrapolating wall, the periodic image —, with the sign of the normal momentum flipped once per reflecting wall crossed.  A level qualifies if
+ *   - it is 3-D and all n_all boxes of the level are this rank's (the level's own boxes),
+ *   - its boxes are equal, at least nghost cells long, whole 64-cell waves wide, and tile the domain as a regular lattice,
+ *   - every domain face is periodic, reflecting or first-order extrapolating for all ncomp components alike, REFLECT_ODD exactly on the normal
+ *     momentum (component 1 + d at a wall normal to d) — no Dirichlet or custom functor, no coarse-fine ghost cells.
+ * *qualifies receives 1 and the level keeps the map (a later call replaces it), or 0 — not an error: the caller fills its ghost cells as before.
+ * Host logic + one small upload; a planning-only context keeps the map on the host.
+ * qk_ghost_source_lookup (host): the source of cell idx, at most a box length outside box `box` — box and index of the valid cell, flip[d] != 0 where
+ * component 1 + d changes sign.
+ * Environment, read by the hosts (quokka_amd/simulation.py, quokka_amd/host/quokka_host.hpp): QK_GHOST_FROM_SOURCE=0 keeps the fills on a qualifying
+ * level too (default 1: a qualifying level's hydro stages of the carried form skip them); the other QK_* switches: QK_FUSEX, QK_PRIM_HANDOFF,
+ * QK_ROW_ALIGN, QK_MARCH_SEGMENTS, QK_PRE_SEGMENTS, QK_SMALL_LEVEL_CELLS, QK_SMALL_MINLEN, QK_GHOST_LOOPBACK, QK_LIB_PATH. */
+int qk_ghost_source_plan(qk_level *lev, const qk_geometry *geom, int nghost, int ncomp, const qk_bcrec *bcs, int n_all, int *qualifies);
+int qk_ghost_source_lookup(qk_level *lev, int box, const int idx[3], int *src_box, int src_idx[3], int flip[3]);
 
 /* ------------------------------------------------------------------ AMR level machinery: data-parallel pieces */
 /* == amrex::Array4<char> (TagBox) */

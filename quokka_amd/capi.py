@@ -20,6 +20,7 @@ ARITH_DIVBY_RECIPOF, ARITH_DIVN, ARITH_RECIPEXACT, ARITH_SQRTN = 0, 1, 2, 3  # q
 COOLING_LIBM_DEVICE, COOLING_LIBM_PORTABLE = 0, 1  # qk_cooling_set_libm
 RIEMANN_HLLC, RIEMANN_LLF, RIEMANN_HLLD = 0, 1, 2
 LIMITER_MINMOD, LIMITER_MC = 0, 1
+GHOST_FROM_SOURCE_ON = 0x51475331  # QK_GHOST_FROM_SOURCE_ON: the value of qk_hydro_stage_args::ghost_from_source that switches it on
 BC_REFLECT_ODD, BC_INT_DIR, BC_REFLECT_EVEN, BC_FOEXTRAP, BC_EXT_DIR = -1, 0, 1, 2, 3
 
 K_B = 1.380649e-16
@@ -105,7 +106,8 @@ class StageArgs(C.Structure):
                 ("densityFloor", C.c_double), ("tempFloor", C.c_double), ("use_dual_energy", C.c_int), ("K_visc", C.c_double),
                 ("store_flux_rk2", C.c_int), ("fluxRk2", C.c_void_p * 3), ("rk2_carry_rhs", C.c_int), ("rhs1", C.c_void_p), ("flux_mask", C.c_void_p), ("fofc_pass", C.c_int),
                 ("prim_out", C.c_int), ("prim_in", C.c_int),
-                ("store_vel_rk2", C.c_int), ("velRk2", C.c_void_p * 3)]  # (ctypes zero-initialises: 0 / NULL where nobody sets them)
+                ("store_vel_rk2", C.c_int), ("velRk2", C.c_void_p * 3),
+                ("ghost_from_source", C.c_int)]  # (ctypes zero-initialises: 0 / NULL where nobody sets them)
 
 
 def traits(gamma=1.4, reconstruct_eint=True, ndim=3, mean_molecular_weight=M_U, boltzmann_constant=K_B,
@@ -208,6 +210,9 @@ def lib() -> C.CDLL:
         L.qk_ghost_plan_set_components.argtypes = [vp, C.c_int, C.c_int]
         L.qk_ghost_plan_box_is_remote.argtypes = [vp, C.c_int]
         L.qk_ghost_plan_set_box_remote.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "qk_ghost_source_plan"):  # (absent from a library of an earlier build, QK_LIB_PATH: then no level qualifies and every fill stays)
+        L.qk_ghost_source_plan.argtypes = [vp, P(Geometry), ci, ci, P(BCRec), ci, P(ci)]
+        L.qk_ghost_source_lookup.argtypes = [vp, ci, ci * 3, P(ci), ci * 3, ci * 3]
     if hasattr(L, "qk_tag_relative_gradient"):
         L.qk_tag_relative_gradient.argtypes = [vp, vp, T, vp, vp, ci, C.c_double, C.c_double, ci]
         L.qk_tag_centered_gradient.argtypes = [vp, vp, vp, vp, ci, ci, C.c_double, C.c_double, C.c_double, ci]
@@ -294,6 +299,7 @@ DECLARED_SYMBOLS = [
     "qk_ghost_plan_create", "qk_ghost_plan_destroy", "qk_ghost_plan_num_peers", "qk_ghost_plan_peer", "qk_ghost_plan_num_items", "qk_ghost_plan_item",
     "qk_FillBoundary_local", "qk_FillBoundary_local_int", "qk_FillBoundary_pack", "qk_FillBoundary_unpack", "qk_FillBoundary_pack_int", "qk_FillBoundary_unpack_int", "qk_SumBoundary_local", "qk_SumBoundary_pack", "qk_SumBoundary_unpack", "qk_FillPhysicalBoundary",
     "qk_FillPhysicalBoundary_subset", "qk_ghost_plan_set_components", "qk_ghost_plan_box_is_remote", "qk_ghost_plan_set_box_remote",
+    "qk_ghost_source_plan", "qk_ghost_source_lookup",
     "qk_tag_relative_gradient", "qk_tag_centered_gradient", "qk_avgdown_plan_create", "qk_avgdown_plan_destroy", "qk_avgdown_plan_num_items", "qk_average_down", "qk_PreInterpState", "qk_PostInterpState",
     "qk_interp_plan_create", "qk_interp_plan_destroy", "qk_interp_plan_num_items", "qk_interp_plan_item", "qk_InterpFromCoarse",
     "qk_fluxreg_create", "qk_fluxreg_destroy", "qk_fluxreg_num_items", "qk_fluxreg_item", "qk_fluxreg_reset", "qk_fluxreg_save", "qk_fluxreg_restore", "qk_fluxreg_CrseAdd", "qk_fluxreg_FineAdd",

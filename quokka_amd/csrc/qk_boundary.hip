@@ -473,6 +473,149 @@ int qk_ghost_plan_create(qk_level *lev, qk_ghost_plan **plan_out, const qk_geome
 	return QK_OK;
 }
 
+// The source map of out-of-box cells (qk_ghost_source.hpp) of a level that qualifies; *qualifies = 0 and no error where it does not.
+int qk_ghost_source_plan(qk_level *lev, const qk_geometry *geom, int nghost, int ncomp, const qk_bcrec *bcs, int n_all, int *qualifies)
+{
+	if (lev == nullptr) {
+		return QK_ERR_INVALID;
+	}
+	qk_ctx *ctx = lev->ctx;
+	QK_REQUIRE(ctx, geom && bcs && qualifies && ncomp >= 1 && nghost >= 0, "qk_ghost_source_plan: bad argument");
+	*qualifies = 0;
+	lev->gs_qualifies = 0;
+	// 3-D, all boxes of the level on this rank, hydro components present
+	if (geom->ndim != 3 || lev->ndim != 3 || lev->nboxes == 0 || n_all != lev->nboxes || ncomp < NVAR) {
+		return QK_OK;
+	}
+	int dlo[3], dhi[3], blen[3], nlat[3];
+	int64_t nsites = 1;
+	for (int d = 0; d < 3; ++d) {
+		dlo[d] = geom->domain.lo[d];
+		dhi[d] = geom->domain.hi[d];
+		blen[d] = lev->boxes[0].hi[d] - lev->boxes[0].lo[d] + 1;
+		const int width = dhi[d] - dlo[d] + 1;
+		// (the mirrored or wrapped image of a ghost cell lies in the box next to the wall: boxes at least as long as the ghost width)
+		if (blen[d] < std::max(nghost, 1) || width % blen[d] != 0) {
+			return QK_OK;
+		}
+		nlat[d] = width / blen[d];
+		nsites *= nlat[d];
+	}
+	if (nsites != lev->nboxes || blen[0] % 64 != 0) { // (whole waves along x: the consumer is the fused XY sweep)
+		return QK_OK;
+	}
+	auto site = [&](const int l[3]) { return static_cast<size_t>(l[0] + nlat[0] * (l[1] + nlat[1] * l[2])); };
+	std::vector<int> lat2box(static_cast<size_t>(nsites), -1);
+	std::vector<std::array<int, 3>> latOf(static_cast<size_t>(lev->nboxes));
+	for (int b = 0; b < lev->nboxes; ++b) {
+		int l[3];
+		for (int d = 0; d < 3; ++d) {
+			const int len = lev->boxes[b].hi[d] - lev->boxes[b].lo[d] + 1;
+			const int rel = lev->boxes[b].lo[d] - dlo[d];
+			if (len != blen[d] || rel < 0 || rel % blen[d] != 0 || rel / blen[d] >= nlat[d]) {
+				return QK_OK;
+			}
+			l[d] = rel / blen[d];
+		}
+		if (lat2box[site(l)] != -1) {
+			return QK_OK; // two boxes on one lattice site
+		}
+		lat2box[site(l)] = b;
+		latOf[static_cast<size_t>(b)] = {l[0], l[1], l[2]};
+	}
+	// every domain face: one rule for all components; the only sign flip at a reflecting wall is the normal momentum's
+	enum { WRAP, REFLECT, CLAMP };
+	int rule[3][2];
+	for (int d = 0; d < 3; ++d) {
+		for (int side = 0; side < 2; ++side) {
+			rule[d][side] = -1;
+			for (int n = 0; n < ncomp; ++n) {
+				const int type = (side == 0) ? bcs[n].lo[d] : bcs[n].hi[d];
+				int r;
+				if (geom->periodic[d] != 0) {
+					r = WRAP; // (k_physbc leaves a periodic dimension alone whatever the BCRec says)
+				} else if (type == QK_BC_REFLECT_EVEN || type == QK_BC_REFLECT_ODD) {
+					r = REFLECT;
+					if ((type == QK_BC_REFLECT_ODD) != (n == MX + d)) {
+						return QK_OK;
+					}
+				} else if (type == QK_BC_FOEXTRAP) {
+					r = CLAMP;
+				} else {
+					return QK_OK; // Dirichlet, or an interior face that is not periodic: nothing fills those ghost cells
+				}
+				if (rule[d][side] != -1 && rule[d][side] != r) {
+					return QK_OK;
+				}
+				rule[d][side] = r;
+			}
+		}
+	}
+	std::vector<GhostFace> faces(static_cast<size_t>(lev->nboxes) * 6);
+	for (int b = 0; b < lev->nboxes; ++b) {
+		for (int d = 0; d < 3; ++d) {
+			for (int side = 0; side < 2; ++side) {
+				GhostFace f{b, 0, 1, 0};
+				int l[3] = {latOf[static_cast<size_t>(b)][0], latOf[static_cast<size_t>(b)][1], latOf[static_cast<size_t>(b)][2]};
+				const bool wall = (side == 0) ? (l[d] == 0) : (l[d] == nlat[d] - 1);
+				const int r = wall ? rule[d][side] : WRAP;
+				if (r == REFLECT) {
+					f.a = (side == 0) ? 2 * dlo[d] - 1 : 2 * dhi[d] + 1;
+					f.b = -1;
+					f.flip = 1;
+				} else if (r == CLAMP) {
+					f.a = (side == 0) ? dlo[d] : dhi[d];
+					f.b = 0;
+				} else {
+					const int width = dhi[d] - dlo[d] + 1;
+					f.a = wall ? ((side == 0) ? width : -width) : 0;
+					l[d] = wall ? ((side == 0) ? nlat[d] - 1 : 0) : l[d] + ((side == 0) ? -1 : 1);
+					f.box = lat2box[site(l)];
+				}
+				faces[static_cast<size_t>(ghostFaceSlot(b, d, side))] = f;
+			}
+		}
+	}
+	lev->gs_faces = faces;
+	lev->gs_ncomp = ncomp;
+	if (ctx->device >= 0) {
+		(void)hipFree(lev->d_gs_faces);
+		lev->d_gs_faces = nullptr;
+		QK_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void **>(&lev->d_gs_faces), sizeof(GhostFace) * faces.size()));
+		QK_HIP_CHECK(ctx, hipMemcpy(lev->d_gs_faces, faces.data(), sizeof(GhostFace) * faces.size(), hipMemcpyHostToDevice));
+	}
+	lev->gs_qualifies = 1;
+	*qualifies = 1;
+	return QK_OK;
+}
+
+// host-side lookup in the plan: the valid cell (box, index) whose value the fill leaves in cell idx outside box `box` (at most nghost cells outside per
+// dimension), and the component whose sign it flips per dimension (flip[d] != 0: component 1 + d).  The walk the pre-pass kernel does: x, then y, then z.
+int qk_ghost_source_lookup(qk_level *lev, int box, const int idx[3], int *src_box, int src_idx[3], int flip[3])
+{
+	if (lev == nullptr) {
+		return QK_ERR_INVALID;
+	}
+	qk_ctx *ctx = lev->ctx;
+	QK_REQUIRE(ctx, lev->gs_qualifies != 0, "qk_ghost_source_lookup: the level has no source map (qk_ghost_source_plan)");
+	QK_REQUIRE(ctx, box >= 0 && box < lev->nboxes && idx && src_box && src_idx && flip, "qk_ghost_source_lookup: bad argument");
+	int bb = box;
+	for (int d = 0; d < 3; ++d) {
+		const int lo = lev->boxes[box].lo[d], hi = lev->boxes[box].hi[d]; // (the box reached through another dimension spans the same range in this one)
+		QK_REQUIRE(ctx, idx[d] >= lo - (hi - lo + 1) && idx[d] <= hi + (hi - lo + 1), "qk_ghost_source_lookup: more than a box length outside");
+		src_idx[d] = idx[d];
+		flip[d] = 0;
+		if (idx[d] < lo || idx[d] > hi) {
+			GhostFace const &f = lev->gs_faces[static_cast<size_t>(ghostFaceSlot(bb, d, idx[d] > hi ? 1 : 0))];
+			src_idx[d] = f.a + f.b * idx[d];
+			flip[d] = f.flip;
+			bb = f.box;
+		}
+	}
+	*src_box = bb;
+	return QK_OK;
+}
+
 int qk_ghost_plan_destroy(qk_ghost_plan *plan)
 {
 	if (plan == nullptr) {

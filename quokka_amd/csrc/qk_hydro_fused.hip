@@ -93,6 +93,8 @@ struct SweepArgs {
 	// pass replaces — to rk2Vel (never over v1, for the reason rk2Flux is never F1).  Last in the struct: the offsets the carried form reads stay
 	bool store_vel;
 	qk_array4 *rk2Vel; // of this sweep's direction
+	// qk_hydro_stage_args::ghost_from_source: the level's source map of out-of-box cells (device copy; qk_ghost_source.hpp), read by the GFS instantiations
+	const GhostFace *gface;
 };
 
 QK_DEV auto sarr(SweepArgs const &a, int comp) -> double * { return a.scratch + static_cast<int64_t>(comp) * a.total_cells; }
@@ -190,9 +192,13 @@ QK_DEV auto chiCompressive(double Pm2, double Pm1, double Pp1, double Pp2, Recip
 // an inactive direction is 1 (FlattenShocks takes the minimum over the AMREX_SPACEDIM active directions only, hydro_system.hpp:655-669).
 // (Requesting the next plane's values one plane ahead was measured and rejected in round 5, profiles/round5/ab6_pre_prefetch.txt: the 20 registers of
 // the two in-flight cells spill under the 128-register cap, 0.39 -> 0.42 ... 0.53 ms per launch — the kernel is issue-bound, not latency-bound.)
-template <bool PRIM>
+// GFS (qk_hydro_stage_args::ghost_from_source): nobody filled the ghost cells of U — a cell outside the box is read from the valid cell the fill would
+// have copied (qk_ghost_source.hpp).  A thread's column has ONE source column per run of planes below, inside and above the box (gsColumn): the
+// pointer to it is formed where the march enters such a run, and from there on advances by +-1 plane (0 at an extrapolating wall) — the same
+// number of loads as from a filled fab, from other addresses.  (Assumes what every level of equal boxes has: the arrays of its boxes share strides.)
+template <bool PRIM, bool GFS = false>
 __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, const SGeom *geom, const qk_array4 *U_t, double *scratch, int64_t T, Eos eos, bool re, int nseg,
-							    int xt, int yt, int ndim)
+							    int xt, int yt, int ndim, const GhostFace *gface = nullptr)
 {
 	constexpr bool prim_in = PRIM;
 	const unsigned nblk = gridDim.x, lin = blockIdx.x;
@@ -266,11 +272,73 @@ __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, con
 	auto cellOf = [&](PlaneRaw const &r) -> PlaneCell { return prim_in ? PlaneCell{r.rho, r.mx, r.my, r.mz, r.E} : planeCell(eos, re, r); };
 	int64_t uo = ownIn ? U.idx(oi, oj, zfirst - 3) : 0;
 	int64_t uh = haloIn ? U.idx(hi_, hj, zfirst - 3) : 0;
+	// GFS: the source columns of this thread's two cells (pointer to component 0 in the current plane) and the flips of their x, y momenta (bits 0, 1: own
+	// cell, 2, 3: halo cell); uniform per plane: the source's plane step and the flip of the z momentum
+	RA4::GT *po = nullptr, *ph = nullptr; // (global address space kept: qk_device.hpp, A4)
+	unsigned flips = 0;
+	int64_t kstep = 0;
+	bool flipz = false;
 
 	for (int k = zfirst - 3; k <= zlast + 3; ++k, uo += U.ks, uh += U.ks) {
 		const bool inPlane = (k >= zfirst) && (k <= zlast); // uniform: this plane's x / y results are somebody's output
 		const bool kIn = (k >= fzlo) && (k <= fzhi);	      // uniform: the plane exists in the fab
-		const PlaneCell c = cellOf((ownIn && kIn) ? planeLoad(U, uo) : neutral);
+		if constexpr (GFS) {
+			po += kstep;
+			ph += kstep;
+			if (kIn && (k == max(zfirst - 3, fzlo) || k == bx.lo[2] || k == bx.hi[2] + 1)) { // (uniform) the march enters a run of planes
+				// the z face of this box gives the plane and its step (uniform: the boxes reached through x and y have the same z rule), the walk
+				// x -> y -> z through the face entries gives each cell's source box
+				const bool zout = (k < bx.lo[2]) || (k > bx.hi[2]);
+				const int zside = (k > bx.hi[2]) ? 1 : 0;
+				GhostFace fz{b, 0, 1, 0};
+				if (zout) {
+					fz = gface[ghostFaceSlot(b, 2, zside)];
+				}
+				const int ksrc = fz.a + fz.b * k;
+				kstep = fz.b * U.ks;
+				flipz = (fz.flip != 0);
+				auto column = [&](int ci, int cj, unsigned &fl) -> RA4::GT * {
+					int bb = b, is = ci, js = cj;
+					fl = 0;
+					if (ci < bx.lo[0] || ci > bx.hi[0]) {
+						const GhostFace f = gface[ghostFaceSlot(bb, 0, (ci > bx.hi[0]) ? 1 : 0)];
+						is = f.a + f.b * ci;
+						fl |= (f.flip != 0) ? 1u : 0u;
+						bb = f.box;
+					}
+					if (cj < bx.lo[1] || cj > bx.hi[1]) {
+						const GhostFace f = gface[ghostFaceSlot(bb, 1, (cj > bx.hi[1]) ? 1 : 0)];
+						js = f.a + f.b * cj;
+						fl |= (f.flip != 0) ? 2u : 0u;
+						bb = f.box;
+					}
+					if (zout) {
+						bb = gface[ghostFaceSlot(bb, 2, zside)].box;
+					}
+					RA4 Us(U_t[bb]);
+					return Us.p + Us.idx(is, js, ksrc);
+				};
+				unsigned fo = 0, fh = 0;
+				po = ownIn ? column(oi, oj, fo) : nullptr;
+				ph = haloIn ? column(hi_, hj, fh) : nullptr;
+				flips = fo | (fh << 2);
+			}
+		}
+		auto ownLoad = [&]() -> PlaneRaw {
+			if constexpr (GFS) {
+				PlaneRaw r;
+				const double mx = po[U.ns * MX], my = po[U.ns * MY], mz = po[U.ns * MZ];
+				r.rho = po[U.ns * RHO];
+				r.mx = (flips & 1u) ? -mx : mx;
+				r.my = (flips & 2u) ? -my : my;
+				r.mz = flipz ? -mz : mz;
+				r.E = po[U.ns * ENE];
+				return r;
+			} else {
+				return planeLoad(U, uo);
+			}
+		};
+		const PlaneCell c = cellOf((ownIn && kIn) ? ownLoad() : neutral);
 #pragma unroll
 		for (int m = 0; m < 4; ++m) {
 			Pz[m] = Pz[m + 1];
@@ -302,17 +370,43 @@ __global__ void __launch_bounds__(PT_THREADS, 4) k_pre3(const qk_box *boxes, con
 					// its v_y only in the tile's columns within two rows, its density only on the rim (the shock-strength ratio of chi there):
 					// 2.3 loads per halo cell instead of 5 (the conserved form needs all five to form the pressure)
 					if (haloIn && kIn) {
-						hc.P = U.p[uh + U.ns * ENE];
-						if (hy >= 0 && hy < PT_Y && hx >= -2 && hx < PT_X + 2) {
-							hc.vx = U.p[uh + U.ns * MX];
-						}
-						if (hx >= 0 && hx < PT_X && hy >= -2 && hy < PT_Y + 2) {
-							hc.vy = U.p[uh + U.ns * MY];
-						}
-						if (rimX || rimY) {
-							hc.rho = U.p[uh + U.ns * RHO];
+						if constexpr (GFS) {
+							hc.P = ph[U.ns * ENE];
+							if (hy >= 0 && hy < PT_Y && hx >= -2 && hx < PT_X + 2) {
+								const double v = ph[U.ns * MX];
+								hc.vx = (flips & 4u) ? -v : v;
+							}
+							if (hx >= 0 && hx < PT_X && hy >= -2 && hy < PT_Y + 2) {
+								const double v = ph[U.ns * MY];
+								hc.vy = (flips & 8u) ? -v : v;
+							}
+							if (rimX || rimY) {
+								hc.rho = ph[U.ns * RHO];
+							}
+						} else {
+							hc.P = U.p[uh + U.ns * ENE];
+							if (hy >= 0 && hy < PT_Y && hx >= -2 && hx < PT_X + 2) {
+								hc.vx = U.p[uh + U.ns * MX];
+							}
+							if (hx >= 0 && hx < PT_X && hy >= -2 && hy < PT_Y + 2) {
+								hc.vy = U.p[uh + U.ns * MY];
+							}
+							if (rimX || rimY) {
+								hc.rho = U.p[uh + U.ns * RHO];
+							}
 						}
 					}
+				} else if constexpr (GFS) {
+					PlaneRaw r = neutral;
+					if (haloIn && kIn) {
+						const double mx = ph[U.ns * MX], my = ph[U.ns * MY], mz = ph[U.ns * MZ];
+						r.rho = ph[U.ns * RHO];
+						r.mx = (flips & 4u) ? -mx : mx;
+						r.my = (flips & 8u) ? -my : my;
+						r.mz = flipz ? -mz : mz;
+						r.E = ph[U.ns * ENE];
+					}
+					hc = cellOf(r);
 				} else {
 					hc = cellOf((haloIn && kIn) ? planeLoad(U, uh) : neutral);
 				}
@@ -1016,9 +1110,32 @@ template <int NV> QK_DEV void stageEdgeRow(double (*sx)[XW], const EdgeRow<NV> &
 		}
 	}
 }
+// GFS (qk_hydro_stage_args::ghost_from_source): the ghost cells of the input state are not filled — a cell at march position p beyond the box along DIR
+// is read from the valid cell the fill would have copied (qk_ghost_source.hpp).  The source lies in the same column (i, ot) of a box that spans the
+// same transverse range, and the arrays of a qualifying level's boxes share their strides: its offset in the source array is the offset u the cell
+// has in this box's array plus a UNIFORM number of march strides.  So a step beyond the box (a step-uniform branch) only replaces the uniform base of
+// the loads and the sign bit of the normal momentum; the loads themselves are the ones the march always issued — no per-lane index arithmetic, no
+// second copy of the loads for the register allocator to keep apart.
+QK_DEV auto xorSign(double v, unsigned sign) -> double { return __hiloint2double(__double2hiint(v) ^ static_cast<int>(sign), __double2loint(v)); }
+// marchBase: the base the loads of the cell at march position p go through (the lane's offset stays the one in Uin), and the sign bit to flip
+template <bool GFS, int DIR> QK_DEV auto marchBase(SweepArgs const &a, RA4 const &Uin, int b, qk_box const &bx, int p, unsigned &sign) -> RA4::GT *
+{
+	RA4::GT *sp = Uin.p;
+	sign = 0u;
+	if constexpr (GFS) {
+		if (p < bx.lo[DIR] || p > bx.hi[DIR]) {
+			const GhostFace f = a.gface[ghostFaceSlot(b, DIR, (p > bx.hi[DIR]) ? 1 : 0)];
+			const qk_array4 &sd = a.U_in[f.box];
+			sp = (RA4::GT *)sd.p + ((DIR == 1) ? Uin.js : Uin.ks) * ((f.a + f.b * p - sd.begin[DIR]) - (p - ((DIR == 1) ? Uin.by : Uin.bz)));
+			sign = (f.flip != 0) ? 0x80000000u : 0u;
+		}
+	}
+	return sp;
+}
 // the batch pass: the wave-edge faces (x0: the wave's first cell) and halo primitives of the rows row0 .. row0 + XROWS - 1 (clamped to hi) of plane ot
-template <int ORDER, int NS>
-QK_DEV void fusexEdgeBatch(SweepArgs const &a, Eos const &eos, RA4 const &Uin, SGeom const &g, const int64_t (&st)[3], const double *S, int x0, int row0, int hi, int ot, EdgeRow<NVAR + NS> *edge)
+template <int ORDER, int NS, bool GFS>
+QK_DEV void fusexEdgeBatch(SweepArgs const &a, Eos const &eos, RA4 const &Uin, SGeom const &g, int b, qk_box const &bx, const int64_t (&st)[3], const double *S, int x0, int row0, int hi, int ot,
+			   EdgeRow<NVAR + NS> *edge)
 {
 	constexpr int NV = NVAR + NS;
 	const int64_t T = a.total_cells;
@@ -1029,9 +1146,56 @@ QK_DEV void fusexEdgeBatch(SweepArgs const &a, Eos const &eos, RA4 const &Uin, S
 	const int f = x0 + 64 * side; // the face: between cells f - 1 and f
 	int64_t ub = Uin.idx(f - 3, mrow, ot);
 	double qb[6][NV], Uc[NVAR];
+	if constexpr (GFS) {
+		// The three cells left of the box's first column (side 0 of its first chunk) or right of its last (side 1 of its last chunk) come from their
+		// sources: consecutive cells of one row of one box, walked forwards, backwards (mirror) or not at all (extrapolation).  The batch at an interior
+		// chunk boundary finds outL = outR = false.
+		// The base is UNIFORM (the first chunk's left run, the last chunk's right run: one source array each) and the lane's offset ub carries over — the
+		// same row of a box that spans the same rows and planes, same strides, as in marchBase —, so no lane holds a second address.  Every lane first
+		// loads its six cells from this box's array as always (a stale ghost cell is readable memory), then the lanes of that side replace the run.
+		const bool lowChunk = (x0 == bx.lo[0]), highChunk = (x0 + 63 == bx.hi[0]);
+		RA4::GT *bL = Uin.p, *bR = Uin.p;
+		int gL = 1, gR = 1; // the step of the run (+1, -1: mirrored — then the x momentum changes sign —, 0: extrapolated)
+		if (lowChunk) {
+			const GhostFace gf = a.gface[ghostFaceSlot(b, 0, 0)];
+			const qk_array4 &sd = a.U_in[gf.box];
+			bL = (RA4::GT *)sd.p + ((gf.a + gf.b * (x0 - 3) - sd.begin[0]) - (x0 - 3 - Uin.bx));
+			gL = gf.b;
+		}
+		if (highChunk) {
+			const GhostFace gf = a.gface[ghostFaceSlot(b, 0, 1)];
+			const qk_array4 &sd = a.U_in[gf.box];
+			bR = (RA4::GT *)sd.p + ((gf.a + gf.b * (x0 + 64) - sd.begin[0]) - (x0 + 64 - Uin.bx));
+			gR = gf.b;
+		}
 #pragma unroll
-	for (int m = 0; m < 6; ++m, ++ub) {
-		loadPrims<NS>(Uin, ub, eos, a.reconstruct_eint, a.prim_in, qb[m], Uc);
+		for (int m = 0; m < 6; ++m) {
+#pragma unroll
+			for (int n = 0; n < NVAR; ++n) {
+				Uc[n] = Uin.p[ub + m + Uin.ns * n];
+			}
+			if (m < 3) {
+				if (lowChunk && side == 0) {
+#pragma unroll
+					for (int n = 0; n < NVAR; ++n) {
+						Uc[n] = bL[ub + m * gL + Uin.ns * n];
+					}
+					Uc[MX] = xorSign(Uc[MX], static_cast<unsigned>(gL) & 0x80000000u);
+				}
+			} else if (highChunk && side != 0) {
+#pragma unroll
+				for (int n = 0; n < NVAR; ++n) {
+					Uc[n] = bR[ub + 3 + (m - 3) * gR + Uin.ns * n];
+				}
+				Uc[MX] = xorSign(Uc[MX], static_cast<unsigned>(gR) & 0x80000000u);
+			}
+			primsOf<NS>(Uin, ub, eos, a.reconstruct_eint, a.prim_in, Uc, qb[m]);
+		}
+	} else {
+#pragma unroll
+		for (int m = 0; m < 6; ++m, ++ub) {
+			loadPrims<NS>(Uin, ub, eos, a.reconstruct_eint, a.prim_in, qb[m], Uc);
+		}
 	}
 	const int64_t cb = (f - 1 - g.glo[0]) + (mrow - g.glo[1]) * st[1] + (ot - g.glo[2]) * st[2];
 	const double chiL = S[cb], chiR = S[cb + 1];
@@ -1059,10 +1223,11 @@ QK_DEV void fusexEdgeBatch(SweepArgs const &a, Eos const &eos, RA4 const &Uin, S
 		ed[2 * side + 1][n] = (side != 0) ? qb[4][n] : qb[2][n];
 	}
 }
-template <int DIR, int ORDER, int STAGE, bool LAST, int NS, bool CARRY, bool TWOD = false, bool FOFC = false, bool FUSEX = false>
+template <int DIR, int ORDER, int STAGE, bool LAST, int NS, bool CARRY, bool TWOD = false, bool FOFC = false, bool FUSEX = false, bool GFS = false>
 __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos eos)
 {
 	static_assert(!FUSEX || (DIR == 1 && !LAST && !TWOD && !FOFC && CARRY), "the X sweep rides on the Y sweep of a 3-D level in the carried form");
+	static_assert(!GFS || (CARRY && NS == 0 && !TWOD && !FOFC && (FUSEX || DIR == 2)), "ghost_from_source: the fused XY march and the Z march of the carried form");
 	static_assert(!(FOFC && CARRY), "the first-order flux correction pass exists for the reference's form of the RK2 average");
 	static_assert(!TWOD || (DIR == 1 && LAST), "the 2-D build has one marching sweep: y, carrying the epilogue");
 	constexpr int NV = NVAR + NS; // hydro variables + passive scalars
@@ -1161,9 +1326,14 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 	constexpr bool PFQ = !FUSEX && NS == 0; // (with passive scalars the six doubles push 21 instantiations past 256 registers: one wave per SIMD)
 	double Un[NVAR];
 	if constexpr (PFQ) {
+		unsigned sign;
+		RA4::GT *sp = marchBase<GFS, DIR>(a, Uin, b, bx, lo - 3, sign);
 #pragma unroll
 		for (int n = 0; n < NVAR; ++n) {
-			Un[n] = Uin.p[u + Uin.ns * n];
+			Un[n] = sp[u + Uin.ns * n];
+		}
+		if constexpr (GFS) {
+			Un[MX + DIR] = xorSign(Un[MX + DIR], sign);
 		}
 	}
 	for (int step = 0; step < nvalid + 6; ++step, c += ms, u += ums) {
@@ -1178,11 +1348,25 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 		{
 			double Uc[NVAR];
 			if constexpr (PFQ) {
+				unsigned sign;
+				RA4::GT *sp = marchBase<GFS, DIR>(a, Uin, b, bx, lo - 2 + step, sign);
 #pragma unroll
 				for (int n = 0; n < NVAR; ++n) {
 					Uc[n] = Un[n];
-					Un[n] = Uin.p[u + ums + Uin.ns * n];
+					Un[n] = sp[u + ums + Uin.ns * n];
 				}
+				if constexpr (GFS) {
+					Un[MX + DIR] = xorSign(Un[MX + DIR], sign);
+				}
+				primsOf<NS>(Uin, u, eos, a.reconstruct_eint, a.prim_in, Uc, q[4]);
+			} else if constexpr (GFS) {
+				unsigned sign;
+				RA4::GT *sp = marchBase<GFS, DIR>(a, Uin, b, bx, lo - 3 + step, sign);
+#pragma unroll
+				for (int n = 0; n < NVAR; ++n) {
+					Uc[n] = sp[u + Uin.ns * n];
+				}
+				Uc[MX + DIR] = xorSign(Uc[MX + DIR], sign);
 				primsOf<NS>(Uin, u, eos, a.reconstruct_eint, a.prim_in, Uc, q[4]);
 			} else {
 				loadPrims<NS>(Uin, u, eos, a.reconstruct_eint, a.prim_in, q[4], Uc);
@@ -1224,7 +1408,7 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				EdgeRow<NV> *edge = s_edge[threadIdx.y];
 				const int rr = (step - 6) & (XROWS - 1);
 				if (rr == 0) { // (uniform) the wave-edge faces and halo primitives of the next XROWS rows
-					fusexEdgeBatch<ORDER, NS>(a, eos, Uin, g, st, S, bx.lo[0] + bix * 64, cidx[DIR], hi, ot, edge);
+					fusexEdgeBatch<ORDER, NS, GFS>(a, eos, Uin, g, b, bx, st, S, bx.lo[0] + bix * 64, cidx[DIR], hi, ot, edge);
 					waveFence();
 					stageEdgeRow<NV>(sx, edge[0]);
 				}
@@ -1527,7 +1711,9 @@ template <int ORDER, int STAGE, int NS, bool CARRY, bool FOFC = false> void laun
 			return;
 		}
 		if constexpr (CARRY && !FOFC && NS == 0) {
-			if (fusex) {
+			if (fusex && a.gface != nullptr) {
+				hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, false, NS, CARRY, false, FOFC, true, true>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
+			} else if (fusex) {
 				hipLaunchKernelGGL((k_sweep_march<1, ORDER, STAGE, false, NS, CARRY, false, FOFC, true>), grid, dim3(64, MARCH_BY), 0, s, ay, eos);
 			}
 		}
@@ -1542,6 +1728,12 @@ template <int ORDER, int STAGE, int NS, bool CARRY, bool FOFC = false> void laun
 		az.nseg = marchSegments(lev, 2, 1);
 		const dim3 grid((lev->maxlen[0] + 63) / 64, (lev->maxlen[1] + MARCH_BY - 1) / MARCH_BY, lev->nboxes * az.nseg);
 		ProfScope ps(lev->ctx, s, "k_sweep_z");
+		if constexpr (CARRY && !FOFC && NS == 0) {
+			if (a.gface != nullptr) { // (ghost_from_source: qk_hydro_stage_fused has checked that the XY march above took it too)
+				hipLaunchKernelGGL((k_sweep_march<2, ORDER, STAGE, true, NS, CARRY, false, FOFC, false, true>), grid, dim3(64, MARCH_BY), 0, s, az, eos);
+				return;
+			}
+		}
 		hipLaunchKernelGGL((k_sweep_march<2, ORDER, STAGE, true, NS, CARRY, false, FOFC>), grid, dim3(64, MARCH_BY), 0, s, az, eos);
 	}
 }
@@ -1656,6 +1848,18 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 			   "qk_hydro_stage_fused: prim_out belongs to stage 1, prim_in to stage 2 (whose old state is a different array)");
 	}
 
+	const bool gfs = (args->ghost_from_source == QK_GHOST_FROM_SOURCE_ON); // (any other value: off — include/quokka_amd.h)
+	if (gfs) {
+		QK_REQUIRE(ctx, lev->gs_qualifies != 0 && lev->d_gs_faces != nullptr, "qk_hydro_stage_fused: ghost_from_source needs the level's source map (qk_ghost_source_plan found it qualifying)");
+		QK_REQUIRE(ctx, args->rk2_carry_rhs != 0 && args->fofc_pass == 0 && args->flux_mask == nullptr && t->nscalars == 0 && t->ndim == 3,
+			   "qk_hydro_stage_fused: ghost_from_source is the carried form of a 3-D level without flux mask and passive scalars");
+		// a box reads valid cells of its NEIGHBOURS' input arrays while they write their output arrays: no race as long as these are different arrays
+		QK_REQUIRE(ctx, args->U_in != args->U_out, "qk_hydro_stage_fused: ghost_from_source needs U_in and U_out to be different arrays");
+		if (!fusexApplies(lev, SweepArgs{}, true, 0)) { // (QK_FUSEX=0, or boxes that are not whole waves wide: no kernel of the four-launch path reads through the map)
+			return setError(ctx, QK_ERR_UNSUPPORTED, "qk_hydro_stage_fused: ghost_from_source needs the fused XY sweep");
+		}
+	}
+
 	if (int rc = buildGeom(lev); rc != QK_OK) {
 		return rc;
 	}
@@ -1673,7 +1877,12 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 		const int xt = (lev->maxlen[0] + 2 + PT_X - 1) / PT_X, yt = (lev->maxlen[1] + 2 + PT_Y - 1) / PT_Y;
 		const int nseg = prePassSegments(lev, xt, yt);
 		const dim3 grid(static_cast<unsigned>(xt) * yt * lev->nboxes * nseg);
-		if (args->prim_in != 0) {
+		const GhostFace *gface = lev->d_gs_faces;
+		if (gfs && args->prim_in != 0) {
+			hipLaunchKernelGGL((k_pre3<true, true>), grid, dim3(PT_THREADS), 0, s, boxes, geom, args->U_in, scratch, T, eos, re, nseg, xt, yt, t->ndim, gface);
+		} else if (gfs) {
+			hipLaunchKernelGGL((k_pre3<false, true>), grid, dim3(PT_THREADS), 0, s, boxes, geom, args->U_in, scratch, T, eos, re, nseg, xt, yt, t->ndim, gface);
+		} else if (args->prim_in != 0) {
 			hipLaunchKernelGGL(k_pre3<true>, grid, dim3(PT_THREADS), 0, s, boxes, geom, args->U_in, scratch, T, eos, re, nseg, xt, yt, t->ndim);
 		} else {
 			hipLaunchKernelGGL(k_pre3<false>, grid, dim3(PT_THREADS), 0, s, boxes, geom, args->U_in, scratch, T, eos, re, nseg, xt, yt, t->ndim);
@@ -1705,6 +1914,7 @@ int qk_hydro_stage_fused(qk_level *lev, qk_stream stream, const qk_hydro_traits 
 	a.fluxMask = (args->rk2_carry_rhs != 0) ? args->flux_mask : nullptr;
 	a.prim_in = (args->prim_in != 0);
 	a.prim_out = (args->prim_out != 0);
+	a.gface = gfs ? lev->d_gs_faces : nullptr;
 	for (int d = 0; d < 3; ++d) {
 		a.dx3[d] = args->dx[d];
 	}

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "quokka_amd.h"
+#include "qk_ghost_source.hpp"
 
 struct qk_prof_pending {
 	int slot;
@@ -52,6 +53,12 @@ struct qk_level {
 	// qk_cooling.hip: the next-cell counter of the persistent kernel — one per level (a level is used from one stream at a time,
 	// include/quokka_amd.h: two levels cooling on two streams each clear and count their own word)
 	unsigned long long *d_cooling_queue = nullptr;
+	// qk_ghost_source_plan (qk_boundary.hip): the source map of out-of-box cells of a level that qualifies (gs_qualifies) — one entry per box,
+	// dimension and side, host image and device copy; gs_ncomp components were checked
+	int gs_qualifies = 0;
+	int gs_ncomp = 0;
+	std::vector<qk::GhostFace> gs_faces;
+	qk::GhostFace *d_gs_faces = nullptr;
 };
 
 namespace qk

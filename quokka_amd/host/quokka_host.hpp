@@ -524,6 +524,7 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 	// output schedule of AMRSimulation::setInitialConditions / evolve (reference src/simulation.hpp:657-684, 910-941, 983-1003)
 	void outputAfterInitialConditions()
 	{
+		ensureGhostsFilled();
 		if (this->restart_chkfile.empty() && this->checkpointInterval_ > 0) {
 			WriteCheckpointFile();
 		}
@@ -535,16 +536,19 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 	void outputAfterStep(int step)
 	{
 		if (this->plotfileInterval_ > 0 && (step + 1) % this->plotfileInterval_ == 0) {
+			ensureGhostsFilled(); // (plotfiles and checkpoints read ghost cells: derived variables, the checkpointed fabs)
 			lastPlotFileStep_ = step + 1;
 			WritePlotFile();
 		}
 		if (this->checkpointInterval_ > 0 && (step + 1) % this->checkpointInterval_ == 0) { // after the plotfile, like the reference
+			ensureGhostsFilled();
 			lastChkFileStep_ = step + 1;
 			WriteCheckpointFile();
 		}
 	}
 	void outputAfterEvolve()
 	{
+		ensureGhostsFilled();
 		if (this->plotfileInterval_ > 0 && istep[0] > lastPlotFileStep_) {
 			WritePlotFile();
 		}
@@ -1304,6 +1308,59 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 	[[nodiscard]] auto carryActive() const -> bool { return AMREX_SPACEDIM == 3 && rk2CarryRhs_ != 0 && integratorOrder_ == 2 && !storeFluxRk2_ && !forceExactForm_; }
 	bool forceExactForm_ = false; // (set while stage 2 of the carried form is redone in the exact form: correctStage)
 
+	// qk_hydro_stage_args::ghost_from_source: on a level that qualifies (qk_ghost_source_plan, asked once) the fused stages of the carried form read the
+	// cells outside a box from the valid cells the fill would have copied, and launchStage skips the fill.  A plain single-rank, single-level hydro
+	// run only — no hierarchy (regrid, FillPatch and the AMR driver read ghost cells), no overlap groups, no flux mask, no passive scalars, the
+	// default (empty) custom boundary hook.  QK_GHOST_FROM_SOURCE=0 keeps every fill.  While fills are being skipped the state arrays carry stale
+	// ghost cells (ghostsStale_): whatever else reads ghost cells — the first-order correction and the retry on the operators, plotfiles and
+	// checkpoints — calls ensureGhostsFilled() first.
+	int gfsState_ = 0; // 0: not asked yet, 1: applies, 2: does not
+	bool ghostsStale_ = false;
+	[[nodiscard]] auto ghostFromSourceApplies() -> bool
+	{
+		if constexpr (!fusedEligible() || AMREX_SPACEDIM != 3 || HydroSystem<problem_t>::nscalars_ != 0 || is_radiation_enabled_) {
+			return false;
+		} else {
+			if (!carryActive() || fluxMask_.size() > 0 || this->beforePhysBC_ || this->amrLevel_ != 0 || this->customBcIsDefault_ != 1 ||
+			    qkhost::Comm::get().size > 1 || overlapActive()) {
+				return false;
+			}
+			if (gfsState_ == 0) {
+				gfsState_ = 2;
+				char const *e = std::getenv("QK_GHOST_FROM_SOURCE");
+				char const *fx = std::getenv("QK_FUSEX");
+				int maxLevel = 0;
+				amrex::ParmParse("amr").query("max_level", maxLevel);
+				if ((e == nullptr || std::atoi(e) != 0) && (fx == nullptr || std::atoi(fx) != 0) && maxLevel == 0) {
+					auto const bcs = this->boundaryRecords();
+					int q = 0;
+					// (this object's own level: the fill that is being skipped is also what used to activate() it before the launch)
+					qkhost::check(qk_ghost_source_plan(this->levelHandle(), &this->qgeom_, nghost_cc_, static_cast<int>(bcs.size()), bcs.data(),
+									   static_cast<int>(this->allBoxes_.size()), &q),
+						      "qk_ghost_source_plan");
+					gfsState_ = (q != 0) ? 1 : 2;
+				}
+			}
+			return gfsState_ == 1;
+		}
+	}
+	// the ghost cells of the state arrays, if stages with ghost_from_source left them unfilled
+	// (also of `more`: the arrays a stage was handed, where they are copies — a retry's old state)
+	void ensureGhostsFilled(std::initializer_list<amrex::MultiFab const *> more = {})
+	{
+		if (ghostsStale_) {
+			ghostsStale_ = false;
+			this->fillBoundaryConditions(state_old_cc_[0]);
+			this->fillBoundaryConditions(state_inter_cc_);
+			this->fillBoundaryConditions(state_new_cc_[0]);
+			for (auto const *mf : more) {
+				if (mf != &state_old_cc_[0] && mf != &state_inter_cc_ && mf != &state_new_cc_[0]) {
+					this->fillBoundaryConditions(*const_cast<amrex::MultiFab *>(mf));
+				}
+			}
+		}
+	}
+
 	// Boxes of this rank in two groups for the overlapped ghost fill: [0] early — every ghost cell is filled on this GPU —, [1] late — waits
 	// for strips from other ranks (qk_ghost_plan_box_is_remote).  Each group is a sub-level whose descriptor tables alias the level's arrays.
 	struct OverlapGroup {
@@ -1418,8 +1475,9 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 	}
 	// one fused stage over all local boxes (group < 0) or over one group of the overlapped fill
 	// grp / scratch / stream: a sub-level of its own with its own stage scratch on its own stream (the far boxes of a speculative coarse step)
+	// ghostFromSource: the ghost cells of U_in were not filled (launchStage)
 	void fusedLaunch(int stageNo, amrex::MultiFab const &U_in, amrex::MultiFab const &U_old, amrex::MultiFab &U_out, double dt, int group = -1, bool fofc = false,
-			 int slot = 0, OverlapGroup *grp = nullptr, void *scratch = nullptr, int64_t scratchBytes = 0, hipStream_t stream = nullptr)
+			 int slot = 0, OverlapGroup *grp = nullptr, void *scratch = nullptr, int64_t scratchBytes = 0, hipStream_t stream = nullptr, bool ghostFromSource = false)
 	{
 		auto t = qkhost::traits<problem_t>();
 		if (grp == nullptr && group >= 0) {
@@ -1471,6 +1529,7 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 			a.prim_out = (stageNo == 1) ? 1 : 0;
 			a.prim_in = (stageNo == 2) ? 1 : 0;
 		}
+		a.ghost_from_source = ghostFromSource ? QK_GHOST_FROM_SOURCE_ON : 0;
 		qkhost::check(qk_hydro_stage_fused(grp == nullptr ? qkhost::Runtime::get().lev : grp->lev, stream != nullptr ? stream : qkhost::Runtime::get().computeStream(), &t, &a),
 			      "qk_hydro_stage_fused");
 	}
@@ -1519,6 +1578,7 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 	// Euler feeding flux registers (whose halfFlux must hold the corrected flux) —, the whole stage on the operators otherwise
 	auto correctStage(int stageNo, amrex::MultiFab const &U_in, amrex::MultiFab const &U_old, amrex::MultiFab &U_out, double dt) -> bool
 	{
+		ensureGhostsFilled({&U_in, &U_old}); // (the correction passes and the operators read filled ghost cells)
 		if (stageNo == 1) {
 			stage1LeftF1_ = !carryActive();
 		}
@@ -1591,6 +1651,12 @@ template <typename problem_t> class QuokkaSimulation : public AMRSimulation<prob
 		if (overlapActive()) {
 			this->fillBoundaryConditions(U_in, [&]() { fusedLaunch(stageNo, U_in, U_old, U_out, dt, 0, false, slot); });
 			fusedLaunch(stageNo, U_in, U_old, U_out, dt, 1, false, slot);
+			return;
+		}
+		if (ghostFromSourceApplies()) {
+			this->activate(); // (fillBoundaryConditions does it on the other path: the launch below acts on the active level)
+			ghostsStale_ = true; // nobody fills, nobody writes a ghost cell: the kernels read the valid cells the fill would have copied
+			fusedLaunch(stageNo, U_in, U_old, U_out, dt, -1, false, slot, nullptr, nullptr, 0, nullptr, true);
 			return;
 		}
 		this->fillBoundaryConditions(U_in);

@@ -326,6 +326,11 @@ class HydroSimulation:
         self.strang_sources = []  # add_strang_source
         self.ghost = GhostExchange(lev, geom, self.ncomp_cc, NGHOST_CC, self.all_boxes, self.owner, rank, bcs, dirichlet)
         self.flag_ghost = None  # built lazily: only FOFC needs redoFlag.FillBoundary
+        # qk_hydro_stage_args::ghost_from_source: on a level that qualifies (qk_ghost_source_plan, asked once) the fused stages of the carried form read
+        # the cells outside a box from their sources and the two fills of a step are skipped (_ghost_from_source_applies); the array whose fill was
+        # skipped carries `ghost_stale`, and whatever else reads ghost cells fills first (ensure_ghosts_filled).  QK_GHOST_FROM_SOURCE=0: every fill stays.
+        self.ghost_from_source = os.environ.get("QK_GHOST_FROM_SOURCE", "1") != "0"
+        self._gfs_qualifies = None
         nd = geom.ndim
         # half-step fluxes / face velocities of stage 1 (flux_rk2 / avgFaceVel of QuokkaSimulation.hpp:1056-1073)
         self.halfFlux = [MultiFab(lev, self.hydro.nvar_, 0, facedir=d) for d in range(nd)]
@@ -367,6 +372,30 @@ class HydroSimulation:
 
     def fillBoundaryConditions(self, state: MultiFab):
         self.ghost.fill(state)
+        state.ghost_stale = False
+
+    def ensure_ghosts_filled(self, *states: MultiFab):
+        """fill the ghost cells of the arrays whose fill a stage with ghost_from_source skipped: before the first-order correction and the retry on
+        the operators, and before anything outside the hydro stages reads ghost cells of a state array"""
+        for st in states:
+            if getattr(st, "ghost_stale", False):
+                self.fillBoundaryConditions(st)
+
+    def _ghost_from_source_applies(self) -> bool:
+        """the fused stage about to be launched reads out-of-box cells from their sources (qk_hydro_stage_args::ghost_from_source): a plain single-rank
+        hydro level (no hierarchy, no overlap groups) in the carried form on the fused XY sweep, no flux mask, no passive scalars, no Dirichlet
+        faces, whose boxes and boundary rules qualify (qk_ghost_source_plan)"""
+        if not (self.ghost_from_source and type(self) is HydroSimulation and self.nranks == 1 and self.use_fused and self._carry_active()
+                and getattr(self, "flux_mask", None) is None and self.traits.nscalars == 0 and not self._has_dirichlet
+                and os.environ.get("QK_FUSEX", "1").strip() not in ("0", "")):
+            return False
+        if self._gfs_qualifies is None:
+            L, q = self.ctx.L, C.c_int(0)
+            if hasattr(L, "qk_ghost_source_plan"):
+                self.ctx.check(L.qk_ghost_source_plan(self.lev.h, C.byref(self.ghost._geom_c), NGHOST_CC, self.ncomp_cc, self.ghost.bcs, len(self.all_boxes),
+                                                      C.byref(q)), "qk_ghost_source_plan")
+            self._gfs_qualifies = bool(q.value)
+        return self._gfs_qualifies
 
     def set_initial_conditions(self, fn: Callable[[np.ndarray, np.ndarray, np.ndarray], np.ndarray]):
         """fn(i, j, k) -> (ncomp, ...) array of conserved variables on the index grids of a valid box."""
@@ -705,7 +734,7 @@ class HydroSimulation:
         c = self.ctx
         c.check(c.L.qk_clear_bytes(c.h, c.stream(), C.c_void_p(self._dev_words.data_ptr() + (0 if both else 32 * slot)), 64 if both else 32), "qk_clear_bytes")
 
-    def _fused_launch(self, stage: int, U_in, U_old, U_out, dt, group=None, fofc: bool = False, slot: int = 0, scratch=None):
+    def _fused_launch(self, stage: int, U_in, U_old, U_out, dt, group=None, fofc: bool = False, slot: int = 0, scratch=None, ghost_from_source: bool = False):
         """one fused stage over all local boxes (group None) or over a sub-level (Level, [local box indices]); fofc: the first-order flux
         correction pass of a stage whose first pass flagged cells (qk_hydro_stage_args::fofc_pass); slot: the device words it reports in;
         scratch: a scratch array of its own for a launch that runs beside another one of this level (two streams)"""
@@ -747,6 +776,7 @@ class HydroSimulation:
         a.fofc_pass = int(fofc)
         if self._prim_now and not fofc:  # the primitive hand-off between the two stages of this advance (prim_handoff)
             a.prim_out, a.prim_in = int(stage == 1), int(stage == 2)
+        a.ghost_from_source = capi.GHOST_FROM_SOURCE_ON if ghost_from_source else 0  # (_launch_stage: the ghost cells of U_in were not filled)
         c = self.ctx
         c.check(c.L.qk_hydro_stage_fused(lev.h, c.stream(), C.byref(self.traits), C.byref(a)), "qk_hydro_stage_fused")
 
@@ -808,6 +838,10 @@ class HydroSimulation:
         """fillBoundaryConditions(U_in) + the fused launches of one RK stage, nothing read back.  With more than one rank the boxes that need
         nothing from other ranks are advanced while the strips of the others are on the wire (north_star: FillBoundary overlapped with the
         update on a second stream — RCCL's); the reference's fill is blocking (src/QuokkaSimulation.hpp:1099, :1202)."""
+        if self._ghost_from_source_applies():
+            U_in.ghost_stale = True  # nobody fills, nobody writes a ghost cell: the kernels read the valid cells the fill would have copied
+            self._fused_launch(stage, U_in, U_old, U_out, dt, slot=slot, ghost_from_source=True)
+            return
         self._before_fill(stage, dt)
         groups = self.overlap_groups()
         if groups is None:
@@ -816,6 +850,7 @@ class HydroSimulation:
             return
         early, late = groups
         self.ghost.fill(U_in, between=lambda: self._fused_launch(stage, U_in, U_old, U_out, dt, early, slot=slot))
+        U_in.ghost_stale = False
         self._fused_launch(stage, U_in, U_old, U_out, dt, late, slot=slot)
 
     def _finish_stage(self, stage, U_in, U_old, U_out, dt, nbad: int) -> bool:
@@ -851,6 +886,7 @@ class HydroSimulation:
 
     def _correct_stage(self, stage, U_in, U_old, U_out, dt) -> bool:
         """the fused first pass of a stage flagged cells: first-order flux correction, fused where it applies, on the operators otherwise"""
+        self.ensure_ghosts_filled(U_in, U_old)  # (the correction passes and the operators read filled ghost cells)
         if stage == 1:
             self._stage1_left_F1 = not self._carry_active()  # (the first pass stored the uncorrected F1, which is what stage 2 averages)
         ok = self._fofc_fused(stage, U_in, U_old, U_out, dt)
