@@ -836,6 +836,36 @@ int qk_gravity_surface_scatter(qk_ctx *ctx, qk_stream s, const int n[3], const d
  * domain faces.  dx not equal in all directions to 1e-12 relative, lev->ndim != 3: QK_ERR_UNSUPPORTED. */
 int qk_gravity_kick(qk_level *lev, qk_stream s, const int n[3], const double *phi, const double dx[3], double dt, const qk_array4 *state);
 
+/* ------------------------------------------------------------------ CIC particles (one level, one rank, 3-D, cubic cells; qk_cic.hip)
+ * Massive particles that source the potential and move in it (reference src/simulation.hpp:1043-1047, :1107-1216, src/particles/CICParticles.hpp).
+ * AMReX's ParticleToMesh and ParticleInterpolator::Linear are not restated: the discrete operations are this project's definition.
+ * Particle data: structure of arrays in device memory, pos[d] / vel[d] / mass of np doubles.  n, dx: the lattice and spacing of the Poisson solve
+ * (n refused by qk_gravity_num_ghosts: QK_ERR_UNSUPPORTED; dx not equal in all directions to 1e-12 relative: QK_ERR_UNSUPPORTED).  np < 0, or a NULL
+ * pointer with np > 0: QK_ERR_INVALID.  np == 0 launches nothing and returns QK_OK.  All arithmetic FP64, not contracted, in the order written.
+ * The stencil of a particle at x, per direction d:  l_d = (x_d - prob_lo_d) * (1.0 / dx_d) - 0.5;  b_d = floor(l_d);  t_d = l_d - b_d;
+ * w_d = {1.0 - t_d, t_d};  W(ii, jj, kk) = (w_0[ii] * w_1[jj]) * w_2[kk] on the eight cells b + (ii, jj, kk).  It TAKES PART in the deposit iff
+ * -1.0 <= l_d < n[d] in every direction, decided on the doubles before any conversion to an integer. */
+/* keys[p] = (b_0 + 1) + (n[0] + 1) * ((b_1 + 1) + (n[1] + 1) * (b_2 + 1)), the linear index of the base cell on the lattice of possible base cells; a
+ * particle that does not take part gets the sentinel (n[0] + 1)(n[1] + 1)(n[2] + 1). */
+int qk_cic_cell_keys(qk_ctx *ctx, qk_stream s, const int n[3], const double prob_lo[3], const double dx[3], int64_t np, const double *const pos[3],
+		     int64_t *keys);
+/* The deposit, a gather over cells (deterministic, no atomics).  perm[0 .. np): the permutation of a STABLE sort of the keys; offsets[q], q in
+ * [0, (n[0]+1)(n[1]+1)(n[2]+1)]: the first position in the sorted order whose key is >= q (so base cell q's particles are perm[offsets[q] ..
+ * offsets[q + 1]), in ascending storage index).  For every interior cell c that at least one particle reaches:
+ *   rhs(c) = (sum W * (((4.0 * M_PI) * G) * mass)) * (1.0 / (dx[0] * dx[1] * dx[2])),
+ * the sum from 0.0 over the source base cells b = c - (ii, jj, kk), kk outermost and ii fastest, within one base cell in the order of perm.  rhs: the
+ * dense array of the Poisson solve (the caller zeroes it; qk_gravity_fill_rhs then adds the gas).  A cell no particle reaches is not written; a weight
+ * that falls outside the domain is dropped and never written into the ghost layer.  Cost: proportional to the fullest eight-cell neighbourhood. */
+int qk_cic_deposit(qk_ctx *ctx, qk_stream s, const int n[3], const double prob_lo[3], const double dx[3], double G, int64_t np,
+		   const double *const pos[3], const double *mass, const int64_t *perm, const int64_t *offsets, double *rhs);
+/* The half kick of every particle (taking part or not) from the dense potential phi of the last solve: for d = 0, 1, 2 and the eight stencil cells
+ * (kk outermost, ii fastest), each index clamped to [0, n[e] - 1]:  a_d = -0.5 * (1.0 / dx_d) * (phi(c + e_d) - phi(c - e_d));
+ * vel_d += (0.5 * dt) * (W * a_d).  phi(c +- e_d) reads the face-adjacent ghost layer on the domain faces, never an edge or corner. */
+int qk_cic_kick(qk_ctx *ctx, qk_stream s, const int n[3], const double prob_lo[3], const double dx[3], double dt, const double *phi, int64_t np,
+		const double *const pos[3], double *const vel[3]);
+/* pos_d += dt * vel_d */
+int qk_cic_drift(qk_ctx *ctx, qk_stream s, double dt, int64_t np, double *const pos[3], const double *const vel[3]);
+
 #ifdef __cplusplus
 }
 #endif

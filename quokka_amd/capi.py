@@ -277,6 +277,11 @@ def lib() -> C.CDLL:
     L.qk_gravity_surface_potential.argtypes = [vp, vp, i3, vp, vp, vp, C.c_int64]
     L.qk_gravity_surface_scatter.argtypes = [vp, vp, i3, vp, vp]
     L.qk_gravity_kick.argtypes = [vp, vp, i3, vp, cd * 3, cd, vp]
+    # CIC particles (csrc/qk_cic.hip): no hasattr guard either
+    L.qk_cic_cell_keys.argtypes = [vp, vp, i3, cd * 3, cd * 3, C.c_int64, vp * 3, vp]
+    L.qk_cic_deposit.argtypes = [vp, vp, i3, cd * 3, cd * 3, cd, C.c_int64, vp * 3, vp, vp, vp, vp]
+    L.qk_cic_kick.argtypes = [vp, vp, i3, cd * 3, cd * 3, cd, vp, C.c_int64, vp * 3, vp * 3]
+    L.qk_cic_drift.argtypes = [vp, vp, cd, C.c_int64, vp * 3, vp * 3]
     _lib = L
     return L
 
@@ -311,6 +316,7 @@ DECLARED_SYMBOLS = [
     "qk_tracer_plan_create_refined", "qk_tracer_plan_set_parent", "qk_tracer_plan_set_time_weights", "qk_tracer_plan_clear_parent", "qk_tracer_Where",
     "qk_gravity_scratch_bytes", "qk_gravity_num_ghosts", "qk_gravity_fill_rhs", "qk_gravity_dirichlet_solve", "qk_gravity_surface_gather",
     "qk_gravity_surface_potential", "qk_gravity_surface_scatter", "qk_gravity_kick",
+    "qk_cic_cell_keys", "qk_cic_deposit", "qk_cic_kick", "qk_cic_drift",
 ]
 
 

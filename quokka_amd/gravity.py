@@ -106,8 +106,9 @@ class PoissonSolver:
                 "qk_gravity_kick")
 
 
-def check_supported(sim):
-    """what the self-gravity solver is built for: a plain HydroSimulation, one rank, 3-D, cubic cells, no CIC particles — refused by name otherwise"""
+def check_supported(sim, need_cic_container: bool = True):
+    """what the self-gravity solver is built for: a plain HydroSimulation, one rank, 3-D, cubic cells; CIC particles (do_cic_particles) with their
+    container in place (need_cic_container = False: the call that creates it) — refused by name otherwise"""
     from .simulation import HydroSimulation
     if type(sim) is not HydroSimulation:
         raise capi.QkError(f"doPoissonSolve_: self-gravity is built for HydroSimulation (one level, hydro only), not for {type(sim).__name__}")
@@ -118,5 +119,6 @@ def check_supported(sim):
     dx = sim.geom.dx
     if any(not (abs(dx[d] - dx[0]) <= 1.0e-12 * abs(dx[0])) for d in (1, 2)):
         raise capi.QkError(f"doPoissonSolve_: self-gravity is built for cubic cells (dx equal in all directions to 1e-12 relative), not dx = {dx}")
-    if getattr(sim, "do_cic_particles", 0):
-        raise capi.QkError("doPoissonSolve_: CIC particles (do_cic_particles) are not built: nothing deposits them into the Poisson right-hand side")
+    if getattr(sim, "do_cic_particles", 0) and need_cic_container and getattr(sim, "CICParticles", None) is None:
+        raise capi.QkError("doPoissonSolve_: CIC particles (do_cic_particles) have no container: the switch was set after set_initial_conditions, "
+                           "which creates it — call InitCICParticles()")

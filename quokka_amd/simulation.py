@@ -303,7 +303,13 @@ class HydroSimulation:
         self.Gconst_ = 6.67430e-8  # C::Gconst (cgs) of the reference's constants
         self.reltolPoisson_ = 1.0e-5
         self.abstolPoisson_ = 1.0e-5
-        self.do_cic_particles = 0  # (not built: refused by name together with doPoissonSolve_)
+        # massive CIC particles (reference src/simulation.hpp:652-653, :870-886, :2007-2016; quokka_amd/cic.py): set it, with
+        # doPoissonSolve_ and createInitialParticles, before set_initial_conditions, which then creates `CICParticles` and has the callable
+        # f(sim) fill it.  The particles are deposited into the Poisson right-hand side before the gas and take a leapfrog step around the
+        # hydro advance.  0 (default): nothing is allocated, nothing is launched.
+        self.do_cic_particles = 0
+        self.CICParticles = None
+        self.createInitialParticles = None
         self.phi = None            # the dense potential (N2+2, N1+2, N0+2), ghost layer = boundary data; None until solved
         self.poisson = None        # gravity.PoissonSolver, created by the first solve
         self.on_gravity = None     # test hook: on_gravity(sim, dt) between the solve and the kick of ellipticSolveAllLevels
@@ -407,13 +413,15 @@ class HydroSimulation:
         self.state_old_cc_.copy_from(self.state_new_cc_)
         if self.do_tracers:
             self.InitTracerParticles()
+        if self.do_cic_particles:
+            self.InitCICParticles()  # (reference src/simulation.hpp:652-653: before the first potential, which they source)
         if self.doPoissonSolve_:
             self.calculateGpotAllLevels()  # (reference src/simulation.hpp:665)
 
     # ------------------------------------------------------------------ self-gravity
     def calculateGpotAllLevels(self):
-        """phi from the density of state_new_cc_ (reference src/simulation.hpp:1011-1069): rhs = 0; rhs += 4 pi G rho; open-boundary solve to
-        max(reltolPoisson_ * max rhs, abstolPoisson_ * min rhs).  A solve that does not converge raises."""
+        """phi from the density of state_new_cc_ (reference src/simulation.hpp:1011-1069): rhs = 0; the CIC particles' deposit (do_cic_particles);
+        rhs += 4 pi G rho; open-boundary solve to max(reltolPoisson_ * max rhs, abstolPoisson_ * min rhs).  A solve that does not converge raises."""
         if not self.doPoissonSolve_:
             return
         from . import gravity
@@ -422,6 +430,8 @@ class HydroSimulation:
             self.poisson = gravity.PoissonSolver(self.ctx, self.geom.n_cell, self.geom.dx[0])
         ps = self.poisson
         ps.zero_rhs()
+        if self.do_cic_particles:
+            self.CICParticles.deposit(ps, self.Gconst_)  # (reference src/simulation.hpp:1043-1047: before the gas)
         ps.fill_rhs(self.lev, self.state_new_cc_, self.Gconst_, 0)
         ps.solve_open(self.reltolPoisson_, self.abstolPoisson_)
         self.phi = ps.phi
@@ -444,6 +454,43 @@ class HydroSimulation:
         if self.on_gravity is not None:
             self.on_gravity(self, dt)
         self.gravAccelAllLevels(dt)
+
+    # ------------------------------------------------------------------ CIC particles
+    def _check_cic(self, need_container: bool = True):
+        """what the CIC particles are built for: the ground of the self-gravity solver, with doPoissonSolve_ set — refused by name otherwise"""
+        if not self.doPoissonSolve_:
+            raise capi.QkError("do_cic_particles: CIC particles need doPoissonSolve_ = 1 (without the solve the kick would read an empty potential)")
+        from . import gravity
+        gravity.check_supported(self, need_cic_container=need_container)
+
+    def InitCICParticles(self):
+        """the container, then createInitialParticles(sim), then Redistribute (reference src/simulation.hpp:2007-2016).  Called by
+        set_initial_conditions when do_cic_particles is set; a caller that sets the switch later calls it itself."""
+        if not self.do_cic_particles:
+            raise capi.QkError("InitCICParticles: do_cic_particles is 0")
+        self._check_cic(need_container=False)
+        if self.createInitialParticles is None:
+            raise capi.QkError("do_cic_particles: CIC particles need createInitialParticles, a callable f(sim) that fills sim.CICParticles")
+        from .cic import CICParticles
+        self.CICParticles = CICParticles(self)
+        self.createInitialParticles(self)
+        self.CICParticles.redistribute()
+
+    def kickParticlesAllLevels(self, dt: float):
+        """vel += 0.5 dt * acceleration from the potential as it stands (reference src/simulation.hpp:1107-1193)"""
+        if not self.do_cic_particles:
+            return
+        self._check_cic()
+        if self.phi is None:
+            raise capi.QkError("kickParticlesAllLevels: CIC particles have no potential to move in (calculateGpotAllLevels has not run)")
+        self.CICParticles.kick(self.phi, dt)
+
+    def driftParticlesAllLevels(self, dt: float):
+        """pos += dt * vel (reference src/simulation.hpp:1195-1216)"""
+        if not self.do_cic_particles:
+            return
+        self._check_cic()
+        self.CICParticles.drift(dt)
 
     def InitTracerParticles(self):
         """one tracer per valid cell, at the cell centre: InitOnePerCell(0.5, 0.5, 0.5) (reference src/simulation.hpp:1993-2005).  Called by
@@ -1088,13 +1135,20 @@ class HydroSimulation:
             self.dt_ = dt
         if self.do_tracers and self.tracers is None:
             raise capi.QkError("do_tracers was set after set_initial_conditions, which creates the particles: call InitTracerParticles()")
+        if self.do_cic_particles:
+            self.kickParticlesAllLevels(self.dt_)  # kick(1/2) with phi at t (reference src/simulation.hpp:870); refuses what is not built
         self.tNew_ += self.dt_
         self.state_old_cc_, self.state_new_cc_ = self.state_new_cc_, self.state_old_cc_
         ok = self.advanceHydroAtLevelWithRetries(self.dt_)
         if self.do_tracers and self.tracers is not None:
             self.tracers.redistribute()  # Redistribute(lev, lev, ngrow = 0) on level 0 (reference src/simulation.hpp:1317-1329)
+        if self.do_cic_particles:
+            self.CICParticles.redistribute()  # (reference src/simulation.hpp:1330-1341: at the end of the advance, so before the drift)
+            self.driftParticlesAllLevels(self.dt_)  # (reference src/simulation.hpp:880)
         if self.doPoissonSolve_:
             self.ellipticSolveAllLevels(self.dt_)  # (reference src/simulation.hpp:883)
+        if self.do_cic_particles:
+            self.kickParticlesAllLevels(self.dt_)  # kick(1/2) with phi at t + dt (reference src/simulation.hpp:886)
         self.istep += 1
         self.cellUpdates_ += self.CountCells()
         return ok
