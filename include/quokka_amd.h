@@ -866,6 +866,72 @@ int qk_cic_kick(qk_ctx *ctx, qk_stream s, const int n[3], const double prob_lo[3
 /* pos_d += dt * vel_d */
 int qk_cic_drift(qk_ctx *ctx, qk_stream s, double dt, int64_t np, double *const pos[3], const double *const vel[3]);
 
+/* ------------------------------------------------------------------ DiagPDF histograms (one rank, any number of levels; qk_diag.hip)
+ * The weighted N-dimensional histogram of the reference's in-situ diagnostics (src/io/DiagPDF.cpp, DiagBase.cpp, DiagFilter.cpp).  Which cells take
+ * part, the bin of a cell and its weight are the reference's, operation for operation; the ORDER of the sum, which the reference leaves to atomic
+ * adds, is this project's definition, so that the result is deterministic: no floating-point atomics.  All arithmetic FP64, not
+ * contracted, in the order written.  A NULL pointer that is needed or a bad size: QK_ERR_INVALID.  A level without boxes launches nothing.
+ * The cells of a level are ENUMERATED with the box index ascending and, within a box, k outermost and i fastest: e = box_offset[b] + (i - lo_0) +
+ * n_0 * ((j - lo_1) + n_1 * (k - lo_2)). */
+#define QK_DIAG_MAX_VARS 8
+#define QK_DIAG_MAX_FILTERS 8
+/* one histogram axis: component `comp` of the MultiFab `table` (device pointer to the level's descriptors: state components are read in place, a
+ * derived variable lives in a MultiFab of its own).  low_t = log10(low) or low; width_t = (log10(high) - log10(low)) / nbins or (high - low) / nbins,
+ * formed by the caller: the difference first, then one division by (double)nbins. */
+typedef struct qk_diag_var {
+	const qk_array4 *table;
+	int comp;
+	int nbins;
+	int log_spaced;
+	double low_t, width_t;
+} qk_diag_var;
+/* a cell is removed iff value < low || value > high (a NaN keeps it)                                       reference src/io/DiagPDF.cpp:162-169 */
+typedef struct qk_diag_filter {
+	const qk_array4 *table;
+	int comp;
+	double low, high;
+} qk_diag_filter;
+typedef struct qk_diag_pdf {
+	int nvars;    /* 1 .. QK_DIAG_MAX_VARS */
+	int nfilters; /* 0 .. QK_DIAG_MAX_FILTERS */
+	qk_diag_var vars[QK_DIAG_MAX_VARS];
+	qk_diag_filter filters[QK_DIAG_MAX_FILTERS];
+	double weight_fac;	  /* dx_0, (dx_0 * dx_1) or ((dx_0 * dx_1) * dx_2) of the level; 1.0 for cell counts */
+	const qk_array4 *density; /* NULL, or (weighting by mass) the table whose component density_comp multiplies weight_fac */
+	int density_comp;
+} qk_diag_pdf;
+/* makeFineMask at ratio 2 with a zero ghost width                                                          reference src/io/DiagPDF.cpp:149-156
+ * mask: a one-component int array per box without ghost cells.  Every valid cell is set to 1, then the cells of the `nitems` regions are set to 0.
+ * items (DEVICE): 7 ints per region {box, lo_0, lo_1, lo_2, hi_0, hi_1, hi_2}, the intersection of a box of the next level, coarsened by 2, with box
+ * `box` of this level (the caller forms the list); the kernel clips a region to its box, and an item whose box index is out of range is skipped.
+ * max_item_cells: the cell count of the largest region.  nitems == 0: the mask is all 1.  Two launches. */
+int qk_diag_mask(qk_level *lev, qk_stream s, qk_iarray4 *mask, int nitems, const int *items, int64_t max_item_cells);
+/* minimum and maximum of one component over the valid cells of the level (MFVecMin / MFVecMax, one level)    reference src/io/DiagPDF.cpp:251-273
+ * minmax[0 .. 1] (HOST): the result; a level without boxes gives {DBL_MAX, -DBL_MAX}.  A value that is not finite: QK_ERR_STATE.  scratch: a device
+ * allocation of at least qk_diag_minmax_scratch_bytes(lev) bytes.  SYNCHRONOUS: the host reads the three result words. */
+int64_t qk_diag_minmax_scratch_bytes(qk_level *lev); /* -1: lev is NULL */
+int qk_diag_minmax(qk_level *lev, qk_stream s, const qk_array4 *field, int comp, void *scratch, int64_t scratch_bytes, double minmax[2]);
+/* key and weight of every valid cell, at its enumeration index e                                            reference src/io/DiagPDF.cpp:215-239
+ * A cell TAKES PART iff its mask is not 0 (mask NULL: every cell, as on the finest level), no filter removes it, and every variable is in range.
+ * Per variable n, ascending:  val = log10(x) (the device's) or x;  q = (val - low_t) / width_t;  in range iff q >= 0.0 && q < (double)nbins, decided
+ * on the double before any conversion to an integer (a NaN, an infinity or 1e300 is out of range);  bin = (int)floor(q);
+ * cbin = cbin * nbins + bin from cbin = 0: the last variable runs fastest.
+ * keys[e] = cbin, or the sentinel total_bins = prod nbins for a cell that does not take part.  weights[e] = weight_fac, times the density if given
+ * (written for every cell).  box_offset (DEVICE): the enumeration index of the first cell of every box; ncells: the valid cells of the level (a
+ * cell whose e falls outside [0, ncells) is not written).  nbins <= 0: QK_ERR_INVALID; total_bins > 2^24: QK_ERR_UNSUPPORTED. */
+int qk_diag_keys(qk_level *lev, qk_stream s, const qk_diag_pdf *pdf, const qk_iarray4 *mask, const int64_t *box_offset, int64_t ncells, int64_t *keys,
+		 double *weights);
+/* One pass of the sum S of every bin.  S(list): empty -> +0.0; else the list is cut from its start into consecutive blocks of 256, the last one padded
+ * with +0.0; every block is reduced by the tree v[t] = v[t] + v[t + s] for t < s, s = 128, 64, ..., 1; the block results, in order, are the new list;
+ * repeated until one value is left.  This entry reduces `nblocks` blocks, one workgroup of 256 threads each:
+ *   dst[m] = tree(src[perm[blk_start[m] + t]], t < blk_len[m])      (perm NULL: src[blk_start[m] + t])
+ * perm (nperm entries): the permutation of a STABLE sort of the keys, for the first pass over the weights (nsrc entries); later passes run on the
+ * partials with perm NULL.  blk_start / blk_len (DEVICE, the caller's table): a block with blk_len outside 1 .. 256 or not inside the array writes
+ * nothing, so that the caller may launch an upper bound of blocks; an index of perm outside [0, nsrc) contributes a NaN.  copy_single != 0: a block of
+ * ONE value hands it on unchanged — for a pass that some bins no longer need (their S is already one value; the tree would turn a -0.0 into +0.0). */
+int qk_diag_segsum(qk_ctx *ctx, qk_stream s, int64_t nblocks, const int64_t *blk_start, const int64_t *blk_len, const double *src, int64_t nsrc,
+		   const int64_t *perm, int64_t nperm, int copy_single, double *dst);
+
 #ifdef __cplusplus
 }
 #endif

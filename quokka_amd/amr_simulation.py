@@ -722,6 +722,24 @@ class AmrSimulation:
         self.doPoissonSolve_ = 0
         # (tests) called as (lev, time, dt_lev, alpha, beta) just before a level's particles are advected: tracer_fields() is then what the kernel reads
         self.on_tracer_advect: Optional[Callable] = None
+        # in-situ diagnostics (reference src/simulation.hpp:2120-2205; quokka_amd/diagnostics.py), as on HydroSimulation: hydro levels, one
+        # rank; the levels are taken as they stand after the coarse step.  ComputeDerivedVar = f(level_sim, name, out) is called per level.
+        self.m_diagnostics = []
+        self.m_diagVars = []
+        self.derivedNames_ = []
+        self.ComputeDerivedVar = None
+
+    def createDiagnostics(self, params):
+        """reference src/simulation.hpp:2120-2158.  params: the deck keys as diagnostics.parse_deck returns them, or typed by hand"""
+        from . import diagnostics
+        diagnostics.create_diagnostics(self, params)
+
+    def doDiagnostics(self):
+        """reference src/simulation.hpp:2170-2205: every diagnostic that is due at (tNew_, istep[0]) is processed and written; the list of (path, pdf)"""
+        if not self.m_diagnostics:
+            return []
+        from . import diagnostics
+        return diagnostics.do_diagnostics(self)
 
     @property
     def finest_level(self) -> int:
@@ -909,6 +927,8 @@ class AmrSimulation:
             self.AverageDownTo(lev)
         if self.do_tracers:
             self.InitTracerParticles()
+        if self.m_diagnostics:
+            self.doDiagnostics()  # (reference src/simulation.hpp:695-697)
 
     # ------------------------------------------------------------------ tracer particles (DESIGN.md §11 "refined levels")
     def _check_tracers(self):
@@ -1331,6 +1351,8 @@ class AmrSimulation:
     def evolve(self):
         while self.istep[0] < self.maxTimesteps_ and self.tNew_ < self.stopTime_:
             self.step()
+            if self.m_diagnostics:
+                self.doDiagnostics()  # (reference src/simulation.hpp:921)
             if self.tNew_ >= self.stopTime_ - 1.0e-6 * self.dt_[0]:
                 break
 

@@ -97,6 +97,25 @@ class CloudyTables(C.Structure):
                 ("n_nH", C.c_int), ("n_Tgas", C.c_int), ("T_min", C.c_double), ("T_max", C.c_double), ("mmw_min", C.c_double), ("mmw_max", C.c_double)]
 
 
+DIAG_MAX_VARS, DIAG_MAX_FILTERS = 8, 8  # QK_DIAG_MAX_VARS, QK_DIAG_MAX_FILTERS
+
+
+class DiagVar(C.Structure):
+    """qk_diag_var"""
+    _fields_ = [("table", C.c_void_p), ("comp", C.c_int), ("nbins", C.c_int), ("log_spaced", C.c_int), ("low_t", C.c_double), ("width_t", C.c_double)]
+
+
+class DiagFilter(C.Structure):
+    """qk_diag_filter"""
+    _fields_ = [("table", C.c_void_p), ("comp", C.c_int), ("low", C.c_double), ("high", C.c_double)]
+
+
+class DiagPdf(C.Structure):
+    """qk_diag_pdf"""
+    _fields_ = [("nvars", C.c_int), ("nfilters", C.c_int), ("vars", DiagVar * DIAG_MAX_VARS), ("filters", DiagFilter * DIAG_MAX_FILTERS),
+                ("weight_fac", C.c_double), ("density", C.c_void_p), ("density_comp", C.c_int)]
+
+
 class StageArgs(C.Structure):
     _fields_ = [("U_in", C.c_void_p), ("U_old", C.c_void_p), ("U_out", C.c_void_p),
                 ("halfFlux", C.c_void_p * 3), ("halfVel", C.c_void_p * 3),
@@ -282,6 +301,13 @@ def lib() -> C.CDLL:
     L.qk_cic_deposit.argtypes = [vp, vp, i3, cd * 3, cd * 3, cd, C.c_int64, vp * 3, vp, vp, vp, vp]
     L.qk_cic_kick.argtypes = [vp, vp, i3, cd * 3, cd * 3, cd, vp, C.c_int64, vp * 3, vp * 3]
     L.qk_cic_drift.argtypes = [vp, vp, cd, C.c_int64, vp * 3, vp * 3]
+    # DiagPDF histograms (csrc/qk_diag.hip): no hasattr guard either
+    L.qk_diag_mask.argtypes = [vp, vp, vp, ci, vp, C.c_int64]
+    L.qk_diag_minmax_scratch_bytes.argtypes = [vp]
+    L.qk_diag_minmax_scratch_bytes.restype = C.c_int64
+    L.qk_diag_minmax.argtypes = [vp, vp, vp, ci, vp, C.c_int64, cd * 2]
+    L.qk_diag_keys.argtypes = [vp, vp, P(DiagPdf), vp, vp, C.c_int64, vp, vp]
+    L.qk_diag_segsum.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, ci, vp]
     _lib = L
     return L
 
@@ -317,6 +343,7 @@ DECLARED_SYMBOLS = [
     "qk_gravity_scratch_bytes", "qk_gravity_num_ghosts", "qk_gravity_fill_rhs", "qk_gravity_dirichlet_solve", "qk_gravity_surface_gather",
     "qk_gravity_surface_potential", "qk_gravity_surface_scatter", "qk_gravity_kick",
     "qk_cic_cell_keys", "qk_cic_deposit", "qk_cic_kick", "qk_cic_drift",
+    "qk_diag_mask", "qk_diag_minmax_scratch_bytes", "qk_diag_minmax", "qk_diag_keys", "qk_diag_segsum",
 ]
 
 

@@ -310,6 +310,14 @@ class HydroSimulation:
         self.do_cic_particles = 0
         self.CICParticles = None
         self.createInitialParticles = None
+        # in-situ diagnostics (reference src/simulation.hpp:2120-2205; quokka_amd/diagnostics.py): createDiagnostics(params) fills
+        # m_diagnostics and m_diagVars; set_initial_conditions and every step of evolve() then end with doDiagnostics().  derivedNames_ and
+        # ComputeDerivedVar = f(level_sim, name, out) are the reference's hook for derived variables.  Nothing created: nothing is allocated,
+        # nothing is launched.
+        self.m_diagnostics = []
+        self.m_diagVars = []
+        self.derivedNames_ = []
+        self.ComputeDerivedVar = None
         self.phi = None            # the dense potential (N2+2, N1+2, N0+2), ghost layer = boundary data; None until solved
         self.poisson = None        # gravity.PoissonSolver, created by the first solve
         self.on_gravity = None     # test hook: on_gravity(sim, dt) between the solve and the kick of ellipticSolveAllLevels
@@ -417,6 +425,21 @@ class HydroSimulation:
             self.InitCICParticles()  # (reference src/simulation.hpp:652-653: before the first potential, which they source)
         if self.doPoissonSolve_:
             self.calculateGpotAllLevels()  # (reference src/simulation.hpp:665)
+        if self.m_diagnostics:
+            self.doDiagnostics()  # (reference src/simulation.hpp:695-697)
+
+    # ------------------------------------------------------------------ in-situ diagnostics
+    def createDiagnostics(self, params):
+        """reference src/simulation.hpp:2120-2158.  params: the deck keys as diagnostics.parse_deck returns them, or typed by hand"""
+        from . import diagnostics
+        diagnostics.create_diagnostics(self, params)
+
+    def doDiagnostics(self):
+        """reference src/simulation.hpp:2170-2205: every diagnostic that is due at (tNew_, istep) is processed and written; the list of (path, pdf)"""
+        if not self.m_diagnostics:
+            return []
+        from . import diagnostics
+        return diagnostics.do_diagnostics(self)
 
     # ------------------------------------------------------------------ self-gravity
     def calculateGpotAllLevels(self):
@@ -1158,6 +1181,8 @@ class HydroSimulation:
         while self.istep < self.maxTimesteps_ and cur_time < self.stopTime_:
             if not self.step():
                 return False
+            if self.m_diagnostics:
+                self.doDiagnostics()  # (reference src/simulation.hpp:921)
             cur_time = self.tNew_
             if cur_time >= self.stopTime_ - 1.0e-6 * self.dt_:
                 break
