@@ -731,8 +731,9 @@ int qk_cooling_set_libm(qk_ctx *ctx, int libm);
 /* ------------------------------------------------------------------ arithmetic primitives (introspection for tests)
  * The hand-rolled FP64 division and square root of csrc/qk_device.hpp, which every kernel's "same bits as `/` and sqrt" rests on, over n elements in
  * device memory: out[i] = divBy(a[i], recipOf(b[i])), divN(a[i], b[i]), recipExact(b[i]) (d_a not read, may be NULL) or sqrtN(a[i]) (d_b not read,
- * may be NULL).  The kernel calls the functions of qk_device.hpp; it holds no copy of them. */
-enum { QK_ARITH_DIVBY_RECIPOF = 0, QK_ARITH_DIVN = 1, QK_ARITH_RECIPEXACT = 2, QK_ARITH_SQRTN = 3 };
+ * may be NULL); the slope limiters MC(a[i], b[i]) and minmod(a[i], b[i]) in the form the hydro kernels instantiate; divBySpacing(a[i], recipOf(b[i])),
+ * the quotient by a grid spacing that keeps the sign of a zero numerator.  The kernel calls the functions of qk_device.hpp; it holds no copy of them. */
+enum { QK_ARITH_DIVBY_RECIPOF = 0, QK_ARITH_DIVN = 1, QK_ARITH_RECIPEXACT = 2, QK_ARITH_SQRTN = 3, QK_ARITH_MC = 4, QK_ARITH_MINMOD = 5, QK_ARITH_DIVBY_SPACING = 6 };
 int qk_arith_evaluate(qk_ctx *ctx, qk_stream s, int what, int64_t n, const double *d_a, const double *d_b, double *d_out);
 
 /* ------------------------------------------------------------------ tracer particles (one level, one rank; qk_tracer.hip; refined levels: below)

@@ -16,7 +16,7 @@ ERR_UNSUPPORTED = QK_ERR_UNSUPPORTED
 QK_TRACER_PREV, QK_TRACER_CUR, QK_TRACER_MAX_DEPTH = 0, 1, 3  # include/quokka_amd.h
 HOOK_COMPILED = 100  # QK_HOOK_COMPILED: a hook that is the problem's own compiled device function (the library entry points refuse to evaluate it)
 DIR_X1, DIR_X2, DIR_X3 = 0, 1, 2
-ARITH_DIVBY_RECIPOF, ARITH_DIVN, ARITH_RECIPEXACT, ARITH_SQRTN = 0, 1, 2, 3  # qk_arith_evaluate
+ARITH_DIVBY_RECIPOF, ARITH_DIVN, ARITH_RECIPEXACT, ARITH_SQRTN, ARITH_MC, ARITH_MINMOD, ARITH_DIVBY_SPACING = 0, 1, 2, 3, 4, 5, 6  # qk_arith_evaluate
 COOLING_LIBM_DEVICE, COOLING_LIBM_PORTABLE = 0, 1  # qk_cooling_set_libm
 RIEMANN_HLLC, RIEMANN_LLF, RIEMANN_HLLD = 0, 1, 2
 LIMITER_MINMOD, LIMITER_MC = 0, 1

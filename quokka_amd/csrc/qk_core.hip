@@ -8,7 +8,7 @@
 namespace
 {
 
-// qk_arith_evaluate: the division and square-root primitives of qk_device.hpp themselves, element by element
+// qk_arith_evaluate: the division and square-root primitives and the slope limiters of qk_device.hpp themselves, element by element
 __global__ void __launch_bounds__(256) k_arith_evaluate(int what, int64_t n, const double *a, const double *b, double *out)
 {
 	const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -26,8 +26,17 @@ __global__ void __launch_bounds__(256) k_arith_evaluate(int what, int64_t n, con
 	case QK_ARITH_RECIPEXACT:
 		r = qk::recipExact(b[i]);
 		break;
-	default:
+	case QK_ARITH_MC:
+		r = qk::MC(a[i], b[i]);
+		break;
+	case QK_ARITH_MINMOD:
+		r = qk::minmod(a[i], b[i]);
+		break;
+	case QK_ARITH_SQRTN:
 		r = qk::sqrtN(a[i]);
+		break;
+	default:
+		r = qk::divBySpacing(a[i], qk::recipOf(b[i]));
 		break;
 	}
 	out[i] = r;
@@ -244,7 +253,7 @@ int qk_arith_evaluate(qk_ctx *ctx, qk_stream s, int what, int64_t n, const doubl
 	if (ctx == nullptr) {
 		return QK_ERR_INVALID;
 	}
-	QK_REQUIRE(ctx, what >= QK_ARITH_DIVBY_RECIPOF && what <= QK_ARITH_SQRTN, "arith_evaluate: unknown function");
+	QK_REQUIRE(ctx, what >= QK_ARITH_DIVBY_RECIPOF && what <= QK_ARITH_DIVBY_SPACING, "arith_evaluate: unknown function");
 	QK_REQUIRE(ctx, d_out != nullptr && (d_a != nullptr || what == QK_ARITH_RECIPEXACT) && (d_b != nullptr || what == QK_ARITH_SQRTN),
 		   "arith_evaluate: NULL argument");
 	if (n <= 0) {

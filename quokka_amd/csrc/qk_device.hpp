@@ -154,6 +154,16 @@ QK_DEV auto recipExact(double d) -> double
 }
 // n / d for a single numerator: the reciprocal refined for this quotient alone (8 instructions against the 11 of `/`: no div_scale / div_fixup)
 QK_DEV auto divN(double n, double d) -> double { return divBy(n, recipOf(d)); }
+// n / dx for a grid spacing (a positive normal number, its reciprocal refined once per launch) where the SIGN OF A ZERO quotient counts: the
+// divergence of the face velocities is -0 where the reference's `/` gives -0 (gas at rest next to a planted -0 momentum), and it is stored.  The
+// first product n * r already has the sign of n / d — for a zero numerator it IS the quotient — and divBy's result never has the opposite sign
+// unless it is the +0 that the residual fma(-d, -0, -0) = +0 leaves behind: the sign bit of n * r is copied over (one v_bfi_b32).
+QK_DEV auto divBySpacing(double n, Recip const &R) -> double
+{
+	const double q = n * R.r;
+	const double e = __builtin_fma(-R.d, q, n);
+	return __builtin_copysign(__builtin_fma(e, R.r, q), q);
+}
 
 // quokka::EOS<problem_t>, gamma-law, direct association (oracle/eos.hpp variant 0)
 struct Eos {
@@ -295,16 +305,28 @@ QK_DEV void consToPrim(Eos const &eos, bool reconstruct_eint, const double U[NVA
 // (qk_rad_ops.hip); REF = false, the default and what every hydro kernel instantiates, is the one-instruction form: same value for ordered operands.
 QK_DEV auto stdMin(double a, double b) -> double { return (b < a) ? b : a; }
 QK_DEV auto refClamp(double v, double lo, double hi) -> double { return (v < lo) ? lo : (hi < v) ? hi : v; }
+// 0.5 * (sgn(a) + sgn(b)) of the limiters without the integers: the int form costs four compares, two integer signs, an add, v_cvt_f64_i32 and a
+// multiply for a factor that is 0, +-0.5 or +-1.  Here each operand gives h = +-0.5 with ITS sign bit (the sign bit of the operand's high word
+// under the bits of 0.5: one v_bfi_b32), +0 where the operand is neither below nor above zero (+-0 and NaN: sgn() is 0 for both; one ordered
+// compare, one 32-bit select), and the factor is h(a) + h(b) — an exact add.  The halves are SINGLE precision — 0.5f is an inline constant, a
+// 32-bit register each, no zero low word to keep — and the sum is widened by one exact v_cvt_f64_f32.  Same bits as the int form for EVERY pair
+// of operands, NaN included: 0.5 * double(k) is exact for k in -2..2, both forms give +0 for k = 0 (0.5 * double(0), and x + (-x) rounds to +0).
+QK_DEV auto halfSign(double v) -> float
+{
+	const float h = __builtin_copysignf(0.5f, __int_as_float(__double2hiint(v)));
+	return __builtin_islessgreater(v, 0.0) ? h : 0.0f;
+}
+QK_DEV auto halfSgnSum(double a, double b) -> double { return static_cast<double>(halfSign(a) + halfSign(b)); }
 // hyperbolic_system.hpp:58-66
 template <bool REF = false> QK_DEV auto MC(double a, double b) -> double
 {
 	if constexpr (REF) {
 		return 0.5 * (sgn(a) + sgn(b)) * stdMin(0.5 * fabs(a + b), stdMin(2.0 * fabs(a), 2.0 * fabs(b)));
 	} else {
-		return 0.5 * (sgn(a) + sgn(b)) * smin(0.5 * fabs(a + b), smin(2.0 * fabs(a), 2.0 * fabs(b)));
+		return halfSgnSum(a, b) * smin(0.5 * fabs(a + b), smin(2.0 * fabs(a), 2.0 * fabs(b)));
 	}
 }
-QK_DEV auto minmod(double a, double b) -> double { return 0.5 * (sgn(a) + sgn(b)) * smin(fabs(a), fabs(b)); }
+QK_DEV auto minmod(double a, double b) -> double { return halfSgnSum(a, b) * smin(fabs(a), fabs(b)); }
 
 // hyperbolic_system.hpp:337-433 : PPM edges of cell i from q(i-2..i+2).
 //   am -> rightState(i) (left edge of the cell), ap -> leftState(i+1) (right edge)

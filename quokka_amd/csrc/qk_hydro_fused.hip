@@ -1117,6 +1117,12 @@ template <int NV> QK_DEV void stageEdgeRow(double (*sx)[XW], const EdgeRow<NV> &
 // the loads and the sign bit of the normal momentum; the loads themselves are the ones the march always issued — no per-lane index arithmetic, no
 // second copy of the loads for the register allocator to keep apart.
 QK_DEV auto xorSign(double v, unsigned sign) -> double { return __hiloint2double(__double2hiint(v) ^ static_cast<int>(sign), __double2loint(v)); }
+// the refined reciprocal of a launch-uniform spacing (recipOf on the device: the bits `/` itself would form), moved to scalar registers
+QK_DEV auto uniformRecip(double d) -> Recip
+{
+	const Recip R = recipOf(d);
+	return {d, __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(R.r)), __builtin_amdgcn_readfirstlane(__double2loint(R.r)))};
+}
 // marchBase: the base the loads of the cell at march position p go through (the lane's offset stays the one in Uin), and the sign bit to flip
 template <bool GFS, int DIR> QK_DEV auto marchBase(SweepArgs const &a, RA4 const &Uin, int b, qk_box const &bx, int p, unsigned &sign) -> RA4::GT *
 {
@@ -1278,6 +1284,11 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 	int64_t u = Uin.idx(pos[0], pos[1], pos[2]);
 	const int64_t ums = (DIR == 1) ? Uin.js : Uin.ks;
 
+	// The quotients by the spacings (div v) share one refined reciprocal each, formed here once per launch: uniform, kept in scalar registers.  Not
+	// with passive scalars or in the first-order correction pass: those instantiations sit at the 256-register limit and the extra live value spills.
+	constexpr bool RDX = NS == 0 && !FOFC;
+	const Recip Rdx = LAST ? recipOf(RDX ? a.dx : 1.0) : uniformRecip(RDX ? a.dx : 1.0); // (the final sweep is short of scalar registers, not of vector ones)
+	const Recip Rdx0 = uniformRecip(FUSEX ? a.dx0 : 1.0);
 	constexpr int AV = Axes<DIR, TWOD>::v, AW = Axes<DIR, TWOD>::w;
 	double q[5][NV];
 	double apPrev[NV], Fprev[NV];
@@ -1415,7 +1426,9 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				// The X sweep of the row inside the wave: primitives, then right-edge states + D_y, D_z, then fluxes travel through the row buffer.
 				// (These 25 lines stay in the loop body: behind ANY function boundary — a QK_DEV function or a lambda, whatever its parameters — the
 				// same text costs the fused kernel 14 spilled registers and the second wave per SIMD: 254 VGPRs + 14 AGPRs, occupancy 1.)
-				const double Dy = S[(S_AUX + 2) * T + cu];
+				// D_y of the row's cells from the window — v_y of the cell and of both its y neighbours is in registers, and the pre-pass forms D_y from
+				// exactly these operands in this order (fdy[3] in k_pre3) —: no load, no 64-bit address
+				const double Dy = smin(q[2][PVY] - q[1][PVY], q[1][PVY] - q[0][PVY]);
 				const int l = static_cast<int>(threadIdx.x) + 2;
 				putColumn(sx, l, q[1]);
 				waveFence();
@@ -1441,7 +1454,7 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				for (int n = 0; n < NV; ++n) {
 					rhs_in[n] = a.inv_dx0 * (sx[n][lself] - sx[n][lnext]); // hydro_system.hpp:469
 				}
-				rhs_in[NV] = (sx[NV][lnext] - sx[NV][lself]) / a.dx0; // :803
+				rhs_in[NV] = divBySpacing(sx[NV][lnext] - sx[NV][lself], Rdx0); // :803
 				waveFence();
 				if (rr + 1 < XROWS) {
 					stageEdgeRow<NV>(sx, edge[rr + 1]);
@@ -1492,7 +1505,7 @@ __global__ void __launch_bounds__(64 * MARCH_BY) k_sweep_march(SweepArgs a, Eos 
 				for (int n = 0; n < NV; ++n) {
 					rhs[n] = rhs_in[n] + a.inv_dx * (Fprev[n] - F[n]);
 				}
-				const double div_v = rhs_in[NV] + (vf - vfPrev) / a.dx;
+				const double div_v = rhs_in[NV] + (RDX ? divBySpacing(vf - vfPrev, Rdx) : (vf - vfPrev) / a.dx);
 				if (LAST) {
 					if (live) {
 						updateCellFrom<NS, CARRY ? STAGE : 0, FOFC, TWOD ? 2 : 3>(a, eos, ec, b, cidx[0], cidx[1], cidx[2], Uo, rhs, div_v, F1, sig0, sig1,
